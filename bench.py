@@ -16,6 +16,10 @@ multi-rank path on a box with fewer GPUs than ranks (ranks share devices, the ga
 Timing: an untimed ramp (--ramp, default 400 launches; a fresh context runs its first ~100 launches 3-5 % slow), W untimed
 warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks.
 
+A plain run does only what the headline figure needs.  --full adds what takes work of its own: the status check, the roofline
+(kernel time over >= 200 extra launches), the CPU baseline and, for --workload reduced, the full-model kernel timed beside it.
+--dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy (float64).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -85,8 +89,11 @@ def parse_args(argv=None):
                          "(parity-test cases; measured for DESIGN.md only)")
     ap.add_argument("--no-hqp", action="store_true", help="hqp = false: plain hierarchy + closed-form redistribution (DESIGN.md only)")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"], help="arithmetic type of the kernels (f32: measured for DESIGN.md only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the status check, the roofline, the CPU baseline and the reduced path's full-model comparison")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -191,6 +198,22 @@ def rank_inputs(args, rank):
     return cases.synth_batch(args.batch, seed=20251226 + 2 + 1000 * rank, **kw)
 
 
+DUMP_BYTES = 60 * 10**6  # --dump-outputs stays under 64 MB in all (npy headers included)
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> array with one row per instance, written as path/<name>.npy in float64.  Above DUMP_BYTES in all, every
+    array keeps the same share of its rows, a seeded sample in instance order (the same rows from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, a.shape[0] * DUMP_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def rank_main(args, rank, local_rank, world, backend, engine_factory=HipEngine):
     """One rank of the job: warm up, time exactly `steps` solves + the final gather between barriers, return (on rank 0) the
     JSON line and the gathered [tau_total | wrench | status] rows of all ranks.  `engine_factory` is the solver of the rank's
@@ -265,19 +288,27 @@ def rank_main(args, rank, local_rank, world, backend, engine_factory=HipEngine):
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path holds after its last step: this rank's outputs, and the global rows of a gather
+        out = dict(tau=eng.tau, wrench=eng.wrench, status=eng.status)
+        if collective:
+            out["gathered"] = gathered
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
     forced_check = None
     if not collective:
         gathered = shard.pack_outputs_torch(eng.tau, eng.wrench, eng.status)  # (after the timed region: what a gather would have returned)
     elif world == 1:  # forced one-rank collective: what came back through the backend must be this rank's own rows
         forced_check = bool(torch.equal(gathered.cpu(), shard.pack_outputs_torch(eng.tau, eng.wrench, eng.status).cpu()))
-    status_ok = float(eng.status.float().mean().item())
-    kern_ms = eng.kernel_ms(args.steps)
+    status_ok = kern_ms = None
+    if args.full:
+        status_ok = float(eng.status.float().mean().item())
+        kern_ms = eng.kernel_ms(args.steps)
     line = None
     if rank == 0:
         line = make_line(args, world, dt, kern_ms, status_ok, eng.info(), backend)
         if forced_check is not None:
             line["config"]["forced_one_rank_gather_matches_local"] = forced_check
-        if args.workload == "reduced" and engine_factory is HipEngine:
+        if args.full and args.workload == "reduced" and engine_factory is HipEngine:
             # configs[4] names a "reduced centroidal-dynamics fast path": on this kernel it is NOT one (the 39-wide sweeps are shared,
             # the reduced blocks come on top) -- the full-model kernel at the same batch and dtype is timed beside it so that nobody
             # reads the reduced rate as an acceleration
@@ -329,11 +360,13 @@ def make_line(args, world, dt, kern_ms, status_ok, info, backend):
             "batch_per_gpu": B,
             "threads_per_instance": info["threads"],
             "lds_bytes_per_instance": info["lds"],
-            "status_ok_fraction": status_ok,
             "collective_backend": {None: "none (one rank)", "nccl": "rccl"}.get(backend, backend),
             "untimed_ramp_launches": (lambda r: (400 if args.batch <= 4096 else 40) if r < 0 else r)(getattr(args, "ramp", 0)),
         },
-        "roofline": {
+    }
+    if kern_ms is not None:  # --full: the status check and the roofline
+        line["config"]["status_ok_fraction"] = status_ok
+        line["roofline"] = {
             "bound": ROOF_BOUND,
             "achieved": achieved,
             "peak": peak,
@@ -346,8 +379,7 @@ def make_line(args, world, dt, kern_ms, status_ok, info, backend):
             "kernel_ms": kern_ms,
             "flop_per_cycle": f_alg,
             "note": ROOF_NOTE,
-        },
-    }
+        }
     return line
 
 
@@ -404,7 +436,7 @@ def main(argv=None):
             local_rank = local_rank % max(1, torch.cuda.device_count())
     line, _ = rank_main(args, rank, local_rank, world, backend)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.workload == "ds2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "ds2":
             line["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(line), flush=True)
     return 0

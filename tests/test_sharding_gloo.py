@@ -69,7 +69,9 @@ def _worker(rank, world, port, outdir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     args = bench.parse_args(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "19", "--no-cpu-baseline"])
-    line, gathered = bench.rank_main(args, rank, rank, world, "gloo", engine_factory=OracleEngine)
+    # gloo ranks share the devices there are, as bench.main() maps them (rank_main selects its device when one is present)
+    local_rank = rank % max(1, torch.cuda.device_count())
+    line, gathered = bench.rank_main(args, rank, local_rank, world, "gloo", engine_factory=OracleEngine)
     if rank == 0:
         np.save(os.path.join(outdir, "gathered.npy"), gathered.numpy())
         json.dump(line, open(os.path.join(outdir, "line.json"), "w"))
@@ -121,6 +123,43 @@ def test_forced_one_rank_collective_runs_the_gather_branch(tmp_path):
     got = json.load(open(tmp_path / "forced.json"))
     assert got["rows"] == 7 and got["line"]["n_gpus"] == 1
     assert got["line"]["config"]["forced_one_rank_gather_matches_local"] is True
+
+
+def test_bench_plain_line_full_line_and_dumped_outputs(tmp_path):
+    """a plain run's line carries the headline figures only, --full adds the status check and the roofline; --dump-outputs
+    writes the last timed step's tau / wrench / status (float64), which equal one solve of the seeded inputs"""
+    import bench
+    from oracle import orc
+
+    common = ["--steps", "3", "--warmup", "1", "--batch", "6", "--ramp", "0"]
+    args = bench.parse_args(common + ["--dump-outputs", str(tmp_path / "out")])
+    line, _ = bench.rank_main(args, 0, 0, 1, None, engine_factory=OracleEngine)
+    assert line["steps"] == 3 and abs(line["value"] - 6 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+    assert "roofline" not in line and "status_ok_fraction" not in line["config"]
+    q, fl, fs = bench.rank_inputs(args, 0)
+    M = orc.make_model(cases.tocabi_model())
+    S = orc.make_setup(cases.CONTACTS_2, cases.TASKS_2LEVEL, cases.TAU_LIM)
+    tau, wr, st, _ = orc.cycle_batch(M, S, q, fl, fs, 1)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("tau", "wrench", "status")}
+    assert sorted(os.listdir(tmp_path / "out")) == ["status.npy", "tau.npy", "wrench.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["tau"], tau) and np.array_equal(got["wrench"], wr[:, :12]) and np.array_equal(got["status"], st)
+    full, _ = bench.rank_main(bench.parse_args(common + ["--full"]), 0, 0, 1, None, engine_factory=OracleEngine)
+    assert full["config"]["status_ok_fraction"] == float(st.mean()) and full["roofline"]["kernel"] == "oracle stand-in"
+
+
+def test_dump_outputs_samples_the_same_rows_under_the_size_cap(tmp_path, monkeypatch):
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8000)
+    rows = np.arange(100, dtype=np.float64)
+    arrays = dict(a=np.repeat(rows[:, None], 10, axis=1), b=rows.astype(np.int32))  # 8800 bytes as float64
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a, b = np.load(tmp_path / "one" / "a.npy"), np.load(tmp_path / "one" / "b.npy")
+    assert a.shape == (90, 10) and b.shape == (90,) and b.dtype == np.float64 and a.nbytes + b.nbytes <= 8000
+    assert np.array_equal(a[:, 0], b) and (np.diff(b) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "two" / "a.npy"), a) and np.array_equal(np.load(tmp_path / "two" / "b.npy"), b)
 
 
 def test_gather_packed_handles_ragged_slices():
