@@ -8,6 +8,7 @@
 
 #include "dwbc_capi_internal.h"
 #include "dwbc_hqp.h"
+#include "dwbc_setup.h"
 
 using namespace dwbc;
 
@@ -391,6 +392,9 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
     if (reduced && !b->last_reduced) return fail("LQP_R / JACC_R: run the reduced cycle first (DWBC_SOLVE_REDUCED; A_R, G_R, J_I_nc_inv_T come from it)");
     if (!reduced && b->last_reduced) return fail("LQP / JACC: run the full-model cycle first (or use the _r entry points after a reduced one)");
     if (b->su.n_custom > 0 || b->su.has_com_task) return fail("LQP / JACC: link task levels only");
+    // the dump record holds J_task at a stride of kMaxTaskDof rows per level (dwbc_hqp.h): a wider level, or a batch the
+    // general-contact kernel solves (max_active > 2), has no record these configurators can read
+    if (setup_wide_tasks(b->su) || b->max_active > 2) return fail("LQP / JACC: task levels of at most 6 dof");
     if (b->h_flags.empty() || (b->d_flags && !b->own_flags)) return fail("LQP / JACC: contact flags must be set through dwbc_batch_set_contact (the host checks that they are uniform)");
     const int ncn = b->su.n_contacts;
     cfg = LqpCfg{};

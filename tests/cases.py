@@ -4,7 +4,7 @@ package (libdwbc_amd/workloads.py: the bench's product engine imports nothing un
 what only the tests need (golden readers, the oracle's model, pack / URDF-variant helpers)."""
 import os
 
-import numpy as np  # noqa: F401
+import numpy as np
 
 from libdwbc_amd.workloads import (  # noqa: F401
     CONTACTS_2, CONTACTS_4, FOOT_POINT, FSTAR_CASE, Q_CASE, TASK_LINK_6D, TASK_LINK_ROTATION, TASKS_2LEVEL, TASKS_3LEVEL_SWING_L,
@@ -60,3 +60,49 @@ def variant_urdf(path_out, fixed):
     with open(path_out, "w") as f:
         f.write(txt)
     return str(path_out)
+
+
+# ---- hierarchies of one to four levels on the product kernels (every level at most 6 dof: no general-contact kernel)
+TASKS_1LEVEL = [TASKS_2LEVEL[0]]
+# pelvis 6D / upper-body rotation / left hand 6D / right hand 6D: 21 task dof
+TASKS_4LEVEL = TASKS_2LEVEL + [[(TASK_LINK_6D, 23, (0, 0, 0))], [(TASK_LINK_6D, 33, (0, 0, 0))]]
+
+
+def hierarchy_batch(B, levels, seed, yaw=False, free=False, mixed=False):
+    """synth_batch states posed for a hierarchy of `levels` levels.  Returns (tasks, q, flags, fstar).
+    1: pelvis 6D; 2: TASKS_2LEVEL; 3: swing foot (TASKS_3LEVEL_SWING_R, left-foot support: the swing foot cannot also be a
+    contact); 4: TASKS_4LEVEL, the hands' f* a seeded uniform.  mixed: LR / L / R flags per instance (ignored at 3 levels);
+    free: a third of the instances with no active contact."""
+    mode = "L" if levels == 3 else ("mixed" if mixed else "LR")
+    q, flags, fstar = synth_batch(B, seed=seed, yaw=yaw, contact_mode=mode, levels=3 if levels == 3 else 2)
+    if free:
+        flags[::3] = 0
+    if levels == 1:
+        return TASKS_1LEVEL, q, flags, fstar[:, :6].copy()
+    if levels == 2:
+        return TASKS_2LEVEL, q, flags, fstar
+    if levels == 3:
+        return TASKS_3LEVEL_SWING_R, q, flags, fstar
+    hands = 0.5 * np.random.default_rng(seed + 1).uniform(-1, 1, size=(B, 12))
+    return TASKS_4LEVEL, q, flags, np.concatenate([fstar, hands], axis=1)
+
+
+# ---- launch routes of the full-model cycle (dwbc_capi.hip launch()): a test that runs an optional path (dump record, warm start,
+# trajectories, COM / custom levels, hqp = false) at a small batch gets the wide extras build; `capped` forces the build batches
+# beyond four instances per CU run (DWBC_NO_WIDE: the register-capped extras build on the Lds2 map)
+CAPPED_EXTRAS = "dwbc::dwbc_cycle_kernel_v2<39, 34, {L}, 64, true, dwbc::TopoTocabi>"
+
+
+def set_route(monkeypatch, route):
+    assert route in ("natural", "capped"), route
+    for k in ("DWBC_NO_WIDE", "DWBC_NO_PAIR", "DWBC_NO_LEAN", "DWBC_PAIR_ALWAYS"):
+        monkeypatch.delenv(k, raising=False)
+    if route == "capped":
+        monkeypatch.setenv("DWBC_NO_WIDE", "1")
+
+
+def check_route(wbc, route, levels):
+    """after a solve with an optional path on: the capped route really ran the capped extras build"""
+    if route == "capped":
+        assert wbc.kernel_name() == CAPPED_EXTRAS.format(L=levels), wbc.kernel_name()
+        assert wbc.launch_info()[0] == 64

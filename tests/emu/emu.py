@@ -97,7 +97,7 @@ class Emu:
         # compact: True = lean build on the compact LDS map (Lds3); "pair" = the two-wave kernel of dwbc_cycle2p.h, roles run in turn;
         # LDS NaN-poisoned per instance in both
         self.L.emu_set_compact(2 if compact == "pair" else (1 if compact else 0))
-        self.L.emu_set_dense(1 if dense else 0)  # two-level runs: TopoGeneric instantiation (dense A^-1 sweep)
+        self.L.emu_set_dense(1 if dense else 0)  # full build: TopoGeneric instantiation (dense A^-1 sweep)
         cj = None if custom_J is None else np.ascontiguousarray(custom_J, np.float64)  # (B, n_custom, 6, n)
         self.L.emu_set_custom(C.c_void_p(cj.ctypes.data if cj is not None else None))
         tr = None if traj is None else np.ascontiguousarray(traj, np.float64)

@@ -46,14 +46,17 @@ def _run(wbc, q, flags, fstar):
 
 
 @pytest.mark.parametrize("case", [1, 2])
-def test_golden_cases_through_c_abi(case):
-    """reference tests/dwbc_test.cpp CASE 1 / CASE 2 (four registered contacts, two enabled)."""
+def test_golden_cases_through_c_abi(case, monkeypatch, route="natural"):
+    """reference tests/dwbc_test.cpp CASE 1 / CASE 2 (four registered contacts, two enabled).  route (cases.set_route): the
+    dump record runs the extras build -- wide at B = 1, the register-capped one under `capped`."""
+    cases.set_route(monkeypatch, route)
     wbc = _make(1, contacts=cases.CONTACTS_4)
     wbc.enable_dump(True)
     q = np.array([cases.Q_CASE[case]], dtype=np.float64)
     flags = np.array([[1, 1, 0, 0]], dtype=np.uint8)
     fstar = np.array([list(cases.FSTAR_CASE[case][0]) + list(cases.FSTAR_CASE[case][1])])
     tau, wr, st = _run(wbc, q, flags, fstar)
+    cases.check_route(wbc, route, 2)
     g = lambda n: cases.golden(case, n)
     e = lambda a, b: float(np.abs(a - b).max())
     assert st[0] == 1
@@ -68,6 +71,11 @@ def test_golden_cases_through_c_abi(case):
     assert e(tau[0, 0], g("torque_grav_")[:, 0]) < TOL
     assert e(tau[0, 1], g("torque_task_")[:, 0]) < TOL
     assert e(tau[0, 2], g("torque_contact_")[:, 0]) < (1e-8 if case == 1 else 1e-3)
+
+
+@pytest.mark.parametrize("case", [1, 2])
+def test_golden_cases_through_c_abi_capped(case, monkeypatch):
+    test_golden_cases_through_c_abi(case, monkeypatch, route="capped")
 
 
 def test_case3_yaw_invariance_on_device():
@@ -260,12 +268,13 @@ def test_full_size_configs_3_and_4(cfg):
 
 
 @pytest.mark.gpu
-def test_gpu_com_task_hierarchy_vs_oracle():
+def test_gpu_com_task_hierarchy_vs_oracle(monkeypatch, route="natural"):
     """COM position + pelvis rotation + upper-body rotation: the COM link's Jacobian is jac_com_ (reference
     src/dwbc.cpp:352-353); link id = link_num_ = 34, also reachable as model.link_id("COM")"""
     import libdwbc_amd as D
     from oracle import orc
 
+    cases.set_route(monkeypatch, route)
     B = 64
     tasks = [[(3, 34, (0, 0, 0))], [(6, 0, (0, 0, 0))], [(6, 15, (0, 0, 0))]]
     q, fl, _ = cases.synth_batch(B, seed=77, yaw=True)
@@ -283,6 +292,7 @@ def test_gpu_com_task_hierarchy_vs_oracle():
     wbc.set_contact(fl)
     wbc.set_fstar_all(fs)
     wbc.solve()
+    cases.check_route(wbc, route, 3)
     M = orc.make_model(cases.tocabi_model())
     S = orc.make_setup(cases.CONTACTS_2, tasks, cases.TAU_LIM)
     tau, wr, st, _ = orc.cycle_batch(M, S, q, fl, fs, 0)
@@ -292,11 +302,17 @@ def test_gpu_com_task_hierarchy_vs_oracle():
 
 
 @pytest.mark.gpu
-def test_gpu_custom_task_level_vs_oracle():
+def test_gpu_com_task_hierarchy_vs_oracle_capped(monkeypatch):
+    test_gpu_com_task_hierarchy_vs_oracle(monkeypatch, route="capped")
+
+
+@pytest.mark.gpu
+def test_gpu_custom_task_level_vs_oracle(monkeypatch, route="natural"):
     """AddTaskSpace(h, TASK_CUSTOM, dof) + SetTaskSpace(h, f*, J) (reference include/dwbc.h:318,333) through the C-ABI"""
     import libdwbc_amd as D
     from tests.test_kernel_emulation import _custom_case
 
+    cases.set_route(monkeypatch, route)
     B = 16
     q, fl, fs, J, tau, st = _custom_case(B, 43)
     wbc = D.Batch(D.Model.from_urdf(cases.URDF), B, device=0)
@@ -310,10 +326,16 @@ def test_gpu_custom_task_level_vs_oracle():
     wbc.set_fstar(0, fs[:, :6])
     wbc.set_custom_task(1, fs[:, 6:], J)
     wbc.solve()
+    cases.check_route(wbc, route, 2)
     assert (wbc.get("status") == st).all() and st.all()
     assert np.abs(wbc.get("tau") - tau).max() < 1e-6
     with pytest.raises(RuntimeError):
         wbc.solve(reduced=True)
+
+
+@pytest.mark.gpu
+def test_gpu_custom_task_level_vs_oracle_capped(monkeypatch):
+    test_gpu_custom_task_level_vs_oracle(monkeypatch, route="capped")
 
 
 @pytest.mark.gpu
@@ -344,11 +366,12 @@ def test_gpu_copy_kinematics_data():
 
 
 @pytest.mark.gpu
-def test_gpu_hqp_false_vs_oracle():
+def test_gpu_hqp_false_vs_oracle(monkeypatch, route="natural"):
     """hqp = false: plain hierarchy + closed-form redistribution (reference src/dwbc.cpp:856-873, 1570-1619)"""
     import libdwbc_amd as D
     from tests.test_kernel_emulation import _no_hqp_oracle
 
+    cases.set_route(monkeypatch, route)
     B = 32
     q, fl, fs = cases.synth_batch(B, seed=72, yaw=True)
     wbc = D.Batch(D.Model.from_urdf(cases.URDF), B, device=0)
@@ -360,11 +383,17 @@ def test_gpu_hqp_false_vs_oracle():
     wbc.set_contact(fl)
     wbc.set_fstar_all(fs)
     wbc.solve(hqp=False)
+    cases.check_route(wbc, route, 2)
     tau, st = _no_hqp_oracle(q, fl, fs)
     assert (wbc.get("status") == st).all()
     assert np.abs(wbc.get("tau") - tau).max() < 1e-6
     wbc.solve(hqp=True)  # and back
     assert wbc.get("status").mean() > 0.9
+
+
+@pytest.mark.gpu
+def test_gpu_hqp_false_vs_oracle_capped(monkeypatch):
+    test_gpu_hqp_false_vs_oracle(monkeypatch, route="capped")
 
 
 @pytest.mark.gpu
@@ -531,9 +560,10 @@ def test_redundant_task_levels_do_not_abort_the_cascade():
     assert np.abs(wbc.get("tau") - tau).max() < TOL
 
 
-def test_warm_start_sequence_on_device():
+def test_warm_start_sequence_on_device(monkeypatch, route="natural"):
     """dwbc_batch_solve without DWBC_SOLVE_INIT (init = false): working sets carried over in HBM between launches.  A short
     sequence of correlated states: every warm solve equals the cold solve of the same state; active-set steps do not grow."""
+    cases.set_route(monkeypatch, route)
     B = 256
     q, fl, fs = cases.synth_batch(B, seed=78, yaw=True)
     rng = np.random.default_rng(2)
@@ -557,6 +587,11 @@ def test_warm_start_sequence_on_device():
     assert 0 < steps_w <= steps_c
     # cold = a lean build (the two-wave kernel at this batch size, or the one-wave lean kernel), warm = the full build (carries the sets)
     assert ("v2p<" in ref.kernel_name() or "false" in ref.kernel_name()) and "true" in wbc.kernel_name()
+    cases.check_route(wbc, route, 2)
+
+
+def test_warm_start_sequence_on_device_capped(monkeypatch):
+    test_warm_start_sequence_on_device(monkeypatch, route="capped")
 
 
 def test_pipelined_set_state_does_not_tear_the_previous_upload():

@@ -608,3 +608,43 @@ def test_gpu_hqp_level_beyond_working_set_capacity_fails_with_status_0():
             assert np.abs(hq.y_ans(0) - ref.hqp_hs_[0].y_ans_[None]).max() < TOL
         else:
             assert np.abs(hq.y_ans(0)).max() == 0.0
+
+
+@pytest.mark.gpu
+def test_gpu_lqp_and_jacc_refuse_a_batch_the_dump_record_cannot_serve():
+    """The LQP / JACC configurators read J_task from the dump record at kMaxTaskDof (6) rows per level (dwbc_hqp.h).  A level
+    widened past 6 dof after a dumped solve, or a batch switched to the general-contact kernel (three active contacts), has no
+    record they can read: both entry points refuse it instead of reading the rows of the stale record."""
+    import libdwbc_amd as D
+
+    B = 8
+    q, fl, fs = cases.synth_batch(B, seed=35)
+
+    def dumped():
+        wbc = D.Batch(D.Model.from_urdf(cases.URDF), B, device=0)
+        for c in cases.CONTACTS_2:
+            wbc.add_contact(c["link"], c["point"], c["lx"], c["ly"], c["mu"], c["muz"])
+        wbc.add_task(0, D.TASK_LINK_6D, 0)
+        wbc.add_task(1, D.TASK_LINK_ROTATION, 15)
+        wbc.set_torque_limit(np.array(cases.TAU_LIM))
+        wbc.enable_dump(True)
+        wbc.set_state(q); wbc.set_contact(fl); wbc.set_fstar_all(fs)
+        wbc.solve()
+        assert (wbc.get("status") == 1).all()
+        hq = D.HQP.for_lqp(wbc, 12)
+        hq.configure_lqp(wbc)  # the record serves the batch as solved
+        return wbc, hq
+
+    wbc, hq = dumped()
+    wbc.add_task(1, D.TASK_LINK_6D, 23)  # level 1: 3 + 6 = 9 dof
+    assert wbc.task_dof(1) == 9
+    with pytest.raises(D.DwbcError, match="task levels of at most 6 dof"):
+        hq.configure_lqp(wbc)
+    with pytest.raises(D.DwbcError, match="task levels of at most 6 dof"):
+        hq.solve_jacc(wbc, 0)
+    wbc, hq = dumped()
+    wbc.set_max_active_contacts(3)
+    with pytest.raises(D.DwbcError, match="task levels of at most 6 dof"):
+        hq.configure_lqp(wbc)
+    with pytest.raises(D.DwbcError, match="task levels of at most 6 dof"):
+        hq.solve_jacc(wbc, 0)

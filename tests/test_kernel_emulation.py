@@ -58,11 +58,12 @@ def test_redistribution_shortcut_against_the_reference_outputs(case, compact):
 
 
 @pytest.mark.parametrize("compact", [False, True, "pair"])
-@pytest.mark.parametrize("cfg", ["ds", "ds_yaw", "ss_L", "ss_R", "mixed", "nolimit", "free"])
+@pytest.mark.parametrize("cfg", ["ds", "ds_yaw", "ss_L", "ss_R", "mixed", "nolimit", "free", "one_level", "four_levels"])
 def test_emulated_kernel_vs_oracle_batches(cfg, compact):
     """compact = True: the lean build on the 20 KB LDS map (Lds3 of dwbc_cycle2.h: the throughput kernel of batches beyond four
-    instances per CU) with LDS poisoned by NaN before every instance -- a block read before anything wrote it shows in the result."""
-    if compact == "pair" and cfg in ("ss_L", "ss_R"):
+    instances per CU) with LDS poisoned by NaN before every instance -- a block read before anything wrote it shows in the result.
+    one_level / four_levels: pelvis 6D alone, and TASKS_4LEVEL (both hands on levels of their own), mixed contact flags."""
+    if compact == "pair" and cfg in ("ss_L", "ss_R", "four_levels"):
         pytest.skip("the paired (two-wave) kernel is built for one and two task levels")  # "pair": dwbc_cycle2p.h, both roles in turn
     B = 48
     contacts, tasks, lim = cases.CONTACTS_2, cases.TASKS_2LEVEL, cases.TAU_LIM
@@ -84,6 +85,8 @@ def test_emulated_kernel_vs_oracle_batches(cfg, compact):
     q, fl, fs = cases.synth_batch(B, **kw)
     if cfg == "free":
         fl[::3] = 0  # no active contact at all on a third of the batch (the base carries the task forces: Hb = A_bb^-1 in dwbc_cycle2p.h)
+    if cfg in ("one_level", "four_levels"):
+        tasks, q, fl, fs = cases.hierarchy_batch(B, 1 if cfg == "one_level" else 4, seed=1234, yaw=True, mixed=True)
     e = Emu(cases.URDF, contacts, tasks, lim)
     r = e.run(q, fl, fs, compact=compact)
     tau_r, wr_r, st_r, _ = _oracle(q, fl, fs, contacts, tasks, lim)
@@ -363,6 +366,24 @@ def test_tree_sweep_matches_dense_sweep_and_mass_matrix_pattern():
     assert (rt["status"] == rd["status"]).all()
     ok = rt["status"] == 1
     assert np.abs(rt["tau"][ok] - rd["tau"][ok]).max() < 1e-7
+
+
+@pytest.mark.parametrize("levels", [1, 3, 4])
+def test_emulated_dense_sweep_vs_oracle(levels):
+    """The TopoGeneric instantiation (dense A^-1 sweep: any 34-body tree, or DWBC_DENSE_SWEEP) at one, three and four task levels
+    against the oracle and against the TOCABI instantiation of the same states (two levels: test_tree_sweep_matches_...)."""
+    tasks, q, fl, fs = cases.hierarchy_batch(24, levels, seed=4321, yaw=True, free=True)
+    e = Emu(cases.URDF, cases.CONTACTS_2, tasks, cases.TAU_LIM)
+    rd = e.run(q, fl, fs, dense=True)
+    rt = e.run(q, fl, fs)
+    tau_r, wr_r, st_r, _ = _oracle(q, fl, fs, cases.CONTACTS_2, tasks, cases.TAU_LIM)
+    assert (rd["status"] == st_r).all() and (rt["status"] == st_r).all()
+    ok = st_r == 1
+    assert ok.mean() > 0.9
+    assert np.abs(rd["tau"][ok] - tau_r[ok]).max() < 1e-6
+    assert np.abs(rd["wrench"][ok] - wr_r[ok][:, :12]).max() < 1e-5
+    assert np.abs(rd["tau"][ok] - rt["tau"][ok]).max() < 1e-7
+    assert np.abs(tau_r[ok, 1]).max() > 1.0
 
 
 @pytest.mark.parametrize("hqp", [True, False])

@@ -89,9 +89,10 @@ def test_emulated_task_reference_vs_oracle():
 
 
 @pytest.mark.gpu
-def test_gpu_task_reference_vs_oracle():
+def test_gpu_task_reference_vs_oracle(monkeypatch, route="natural"):
     import libdwbc_amd as Dw
 
+    cases.set_route(monkeypatch, route)
     B = 16
     q, qd, fl, fs, ctime, traj0, traj1, fexp = _setup(B, 32)
 
@@ -113,6 +114,7 @@ def test_gpu_task_reference_vs_oracle():
         a.set_trajectory(lv, 0, tr)
     a.set_control_time(ctime)
     a.solve()
+    cases.check_route(a, route, 2)
     b = mk()
     b.set_state(q)
     b.set_fstar_all(fexp)
@@ -130,3 +132,8 @@ def test_gpu_task_reference_vs_oracle():
     c.set_fstar_all(fs)
     c.solve()
     assert np.abs(a.get("tau") - c.get("tau")).max() < 1e-9
+
+
+@pytest.mark.gpu
+def test_gpu_task_reference_vs_oracle_capped(monkeypatch):
+    test_gpu_task_reference_vs_oracle(monkeypatch, route="capped")

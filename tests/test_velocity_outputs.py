@@ -94,9 +94,10 @@ def test_emulated_kernel_velocity_outputs():
 
 
 @pytest.mark.gpu
-def test_gpu_velocity_outputs():
+def test_gpu_velocity_outputs(monkeypatch, route="natural"):
     import libdwbc_amd as Dw
 
+    cases.set_route(monkeypatch, route)
     B = 8
     q, fl, fs = cases.synth_batch(B, seed=6, yaw=True)
     qd = np.random.default_rng(6).uniform(-1, 1, (B, 39))
@@ -111,4 +112,10 @@ def test_gpu_velocity_outputs():
     wbc.set_contact(fl)
     wbc.set_fstar_all(fs)
     wbc.solve()
+    cases.check_route(wbc, route, 2)
     _check(wbc.get("B"), wbc.get("link_v"), wbc.get("link_w"), q, qd)
+
+
+@pytest.mark.gpu
+def test_gpu_velocity_outputs_capped(monkeypatch):
+    test_gpu_velocity_outputs(monkeypatch, route="capped")
