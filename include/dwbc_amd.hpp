@@ -570,7 +570,8 @@ class RobotData {
     bool dirty_ = true, redistributed_ = false, reduced_ = false, hqp_ = true, contact_ok_ = true;
     // general_: more than two contacts flagged at some point, or a task level wider than six dof -- every solve then runs the
     // general-contact kernel (libdwbc_amd/csrc/dwbc_cycle_gc.h), which keeps no dump record: torque_grav_ / torque_task_ / torque_contact_,
-    // getContactForce(total torque) and the int returns are served; the public matrices (A_, J_C, Lambda_contact, ts_[i].J_kt_ ...) are not
+    // getContactForce(total torque), the int returns and link_[0] are served; the public matrices (A_, J_C, Lambda_contact, ts_[i].J_kt_ ...)
+    // are not.  Link and "COM" levels alike (the whole-body harnesses of the reference: COM on level 0, both hands on level 3)
     bool general_ = false;
     Vec wrench_;
     void enter_general() { if (!general_) { general_ = true; dwbc_batch_enable_dump(batch_, 0); dirty_ = true; } }
@@ -640,6 +641,18 @@ class RobotData {
         if (general_) {
             wrench_.assign(dwbc_batch_field_bytes(batch_, DWBC_WRENCH) / 8, 0.0);
             dwbc_batch_get(batch_, DWBC_WRENCH, wrench_.data(), wrench_.size() * 8);
+            // of link_ the base link alone is served here: its pose is the state itself (the reference's harnesses turn f* into the
+            // pelvis frame with link_[0].rotm, tests/sp_test/regulation_test.cpp:97-98)
+            link_.resize(link_num_);
+            if (is_floating_ && link_num_ > 0) {
+                const double x = q_system_[3], y = q_system_[4], z = q_system_[5], w = q_system_[n];
+                const double R[9] = {1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * x * z + 2 * w * y,
+                                     2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x,
+                                     2 * x * z - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y};
+                link_[0].rotm = Mat(3, 3);
+                link_[0].rotm.d.assign(R, R + 9);
+                link_[0].xpos = Vec3(q_system_[0], q_system_[1], q_system_[2]);
+            }
             dirty_ = false;
             return 1;
         }

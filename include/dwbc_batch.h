@@ -147,7 +147,10 @@ int dwbc_batch_size(const dwbc_batch *b);
 int dwbc_batch_add_contact(dwbc_batch *b, int link, int contact_type, const double point[3], double lx, double ly,
                            double mu, double mu_z);
 int dwbc_batch_clear_contacts(dwbc_batch *b);                               /* ClearContactConstraint */
-/* AddTaskSpace(level, mode, link, point) include/dwbc.h:319 (same level twice appends a link, src/dwbc.cpp:592-600) */
+/* AddTaskSpace(level, mode, link, point) include/dwbc.h:319 (same level twice appends a link, src/dwbc.cpp:592-600).
+ * link = dwbc_model_num_links(m) (= dwbc_model_link_id(m, "COM")) is the synthetic COM link.  Two 6D links on one level make a
+ * 12-dof level: such a batch runs the general-contact kernel (see dwbc_batch_set_max_active_contacts), which takes link and COM
+ * levels alike */
 int dwbc_batch_add_task(dwbc_batch *b, int level, int mode, int link, const double point[3]);
 /* AddTaskSpace(heirarchy, TASK_CUSTOM, task_dof) include/dwbc.h:318 and SetTaskSpace(heirarchy, f*, J_task) include/dwbc.h:333:
  * a level whose Jacobian the caller supplies, per instance (fstar: B x task_dof or NULL to keep, J: B x task_dof x ndof row-major) */
@@ -176,8 +179,10 @@ int dwbc_batch_set_state(dwbc_batch *b, const double *q, const double *qdot, con
 int dwbc_batch_set_contact(dwbc_batch *b, const uint8_t *flags);
 /* SetContact with a third flag raised: the reference stacks every flagged contact (src/dwbc.cpp:445-453; its tests register both
  * hands next to the feet, tests/dwbc_test.cpp:68-69).  The product kernels stack two; n = 3 routes every solve of this batch through
- * the general-contact kernel (up to three simultaneously active 6D contacts per instance, hqp = true, link tasks with f* from
- * SetTaskSpace) and widens DWBC_WRENCH to 6 n doubles per instance.  Call before binding a wrench buffer.  n = 2 restores the default. */
+ * the general-contact kernel (up to three simultaneously active 6D contacts per instance, hqp = true, tasks on links and on the
+ * synthetic "COM" link with f* from SetTaskSpace; trajectories, TASK_CUSTOM levels, the dump record, fp32 and the reduced path are
+ * refused at the solve) and widens DWBC_WRENCH to 6 n doubles per instance.  Call before binding a wrench buffer.  n = 2 restores
+ * the default. */
 int dwbc_batch_set_max_active_contacts(dwbc_batch *b, int n);
 int dwbc_batch_max_active_contacts(const dwbc_batch *b);
 /* SetTaskSpace(level, f*) include/dwbc.h:333 : fstar is B x task_dof(level) */

@@ -180,6 +180,8 @@ class Batch:
         return i
 
     def add_task(self, level, mode, link, point=(0.0, 0.0, 0.0)):
+        """AddTaskSpace(level, mode, link, point); ``link = model.link_id("COM")`` is the synthetic COM link.  A second 6D link on a level
+        makes it 12 dof wide: the batch then runs the general-contact kernel, which takes link and COM levels alike."""
         p = np.ascontiguousarray(point, np.float64)
         _check(self._L.dwbc_batch_add_task(self._h, int(level), int(mode), int(link), p.ctypes.data))
 
@@ -248,8 +250,9 @@ class Batch:
 
     def set_max_active_contacts(self, n):
         """Contacts that may be active at once in one instance: 2 (default, the product kernels) or 3 -- every solve of the batch then
-        runs the general-contact kernel (feet + one hand, ...; hqp = true, link tasks) and ``get("wrench")`` is (B, 6 n).  The
-        reference stacks any number of flagged contacts (src/dwbc.cpp:445-453)."""
+        runs the general-contact kernel (feet + one hand, ...; hqp = true, tasks on links and on the synthetic COM link,
+        ``model.link_id("COM")``) and ``get("wrench")`` is (B, 6 n).  Trajectories, TASK_CUSTOM levels, the dump record, fp32 and
+        ``solve(reduced=True)`` are refused there.  The reference stacks any number of flagged contacts (src/dwbc.cpp:445-453)."""
         _check(self._L.dwbc_batch_set_max_active_contacts(self._h, int(n)))
 
     @property

@@ -681,15 +681,15 @@ static int launch_f32(dwbc_batch *b, bool reduced) {
 }
 
 // three active contacts, or a task level of more than six dof: every instance of the batch goes through the general-contact kernel
-// (lean scope); its TG = 12 instantiation when a level is wider than six
+// (lean scope: link tasks and the synthetic COM link); its TG = 12 instantiation when a level is wider than six
 static int launch_gc(dwbc_batch *b) {
     const GcEntry gc_ = find_gc(b->n, b->su.nb), *g = &gc_;
     const bool wide_tasks = setup_wide_tasks(b->su);
     if (!g->fn) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
     if (wide_tasks && !g->fn_wide_tasks) return fail("task levels of more than 6 dof: built in for TOCABI's size only");
     if (!b->hqp) return fail("three active contacts / task levels of more than 6 dof: hqp = true only (the reference's closed-form redistribution is written for two contacts, src/dwbc.cpp:1570-1619)");
-    if (b->su.n_traj > 0 || b->su.has_com_task || b->su.n_custom > 0 || b->dump_on)
-        return fail("three active contacts / task levels of more than 6 dof: link tasks with f* from SetTaskSpace only (no trajectories, COM or custom levels, no dump record)");
+    if (b->su.n_traj > 0 || b->su.n_custom > 0 || b->dump_on)
+        return fail("three active contacts / task levels of more than 6 dof: link and COM tasks with f* from SetTaskSpace only (no trajectories, no TASK_CUSTOM levels, no dump record)");
     auto fn = wide_tasks ? g->fn_wide_tasks : g->fn;
     const int lds_bytes = wide_tasks ? g->lds_bytes_wide_tasks : g->lds_bytes;
     if (b->gc_attr_set != (wide_tasks ? 2 : 1)) {

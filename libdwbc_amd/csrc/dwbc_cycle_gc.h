@@ -80,6 +80,13 @@ struct LdsG {
     static constexpr int Xl = Pc + NCC * 3;           // per level X = J_kt Lambda (M x T)
     static constexpr int Yl = Xl + (kMaxLevels - 1) * M * T;   // per level Y = (J_t A^-1 N_c)[:,6:] (T x M)
     static constexpr int tmp = Yl + (kMaxLevels - 1) * T * M;  // phase-local scratch
+    // jac_com_ of the synthetic COM link (6 x N [linear; angular] + com_pos, as com_jacobian leaves it): only batches with a COM task
+    // level (su.has_com_task) form it.  Stage 0 parks it over Xl / Yl, which the task cascade alone writes; the top of stage 3 moves
+    // it to t_Jcm behind the task-phase scratch, before level 0 writes Xl[0].  The persistent part has no room for it: TG = 6 has
+    // 224 bytes to spare below two workgroups per CU.
+    static constexpr int JcmN = 6 * N + 3;
+    static constexpr int Jcm0 = Xl;
+    static_assert(JcmN <= tmp - Xl, "the parked COM Jacobian fits Xl / Yl");
     // --- scratch, kinematics phase
     static constexpr int k_Rl = tmp;
     static constexpr int k_Iw = k_Rl + NB * 9;
@@ -115,12 +122,15 @@ struct LdsG {
     static constexpr int t_fv = t_F + C * T;          // C
     static constexpr int qp_V = t_fv + C;             // QN
     static constexpr int qp_x = qp_V + QN;            // QN
-    static constexpr int t_end = qp_x + QN;
+    static constexpr int t_Jcm = qp_x + QN;           // jac_com_ through the cascade (inside the contact phase's reach for TG = 6)
+    static constexpr int t_end = t_Jcm + JcmN;
     static constexpr int colA = (tmp + 1) & ~1, colW = (c_s1 + 1) & ~1;  // 16-byte aligned pivot-column buffers of the two big sweeps (64 doubles each)
     static_assert(colA + 64 <= k_end && colW + 64 <= c_s2, "pivot-column buffers");
     static constexpr int total = max2(max2(k_end, c_end), t_end);
     static constexpr int total_bytes = total * (int)sizeof(real_t) + 64;
 };
+// 160 KiB of LDS per CU: the TG = 6 map of TOCABI's size keeps two workgroups per CU (the TG = 12 map runs one)
+static_assert(LdsG<39, 34, 3>::total_bytes <= 81920, "LdsG<39, 34, 3>: two workgroups per CU");
 
 // SPD inverse with one column per lane in registers (the symmetric sweep of dwbc_cycle2.h), any size up to 56: Sin NN x NN (ld) ->
 // Out (ldo).  Same arithmetic role as Eigen's llt().solve(I) (reference src/dwbc.cpp:307).
@@ -348,6 +358,14 @@ DWBC_DEV void qp_rows_and_solve_gc(const Setup &su, int nlim, int ncone, const i
     DWBC_SYNC();
 }
 
+// rows of a COM task level into the row-major task Jacobian Jt (T x N) of this kernel (com_task_rows of dwbc_cycle.h writes the
+// transposed form of the product kernels): rsel 0 -> 6 rows, 1 -> linear, 2 -> angular
+template <int N, int NT>
+DWBC_DEV void com_task_rows_rm(Thr th, const real_t *Jcm, real_t *Jt, int row0, int rsel) {
+    const int nr = rsel == 0 ? 6 : 3, src0 = rsel == 2 ? 3 : 0;
+    for (int idx = th.tid; idx < nr * N; idx += NT) Jt[row0 * N + idx] = Jcm[src0 * N + idx];
+}
+
 // ----------------------------------------------------------------------------------------------
 // the cycle for one instance
 // ----------------------------------------------------------------------------------------------
@@ -523,6 +541,8 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
         }
         DWBC_SYNC();
         for (int j = th.tid; j < N; j += NT) L[S::G + j] = kGrav * A[2 * N + j];  // G_ = -J_com_lin^T m g (dwbc.cpp:358)
+        // jac_com_ = SI_body^-1 CMM_ (dwbc.cpp:318-353) for COM task levels, while the staged A is intact (the inverse below is in place)
+        if (su.has_com_task) com_jacobian<N, NT>(th, A, N, Rw, L + S::q, L + S::Jcm0);
     }
     DWBC_STAMP(0);  // kinematics + CRBA
     int st_contact = 1;
@@ -683,6 +703,8 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
     const int ncone = 10 * nc;
     int st_task = 1, fail_level = -1;
     const io_t *fs_in = io.fstar + (size_t)inst * su.fstar_total;
+    if (su.has_com_task)  // out of Xl / Yl before the first level writes them (the contact scratch under t_Jcm is dead: stage 2 fenced)
+        for (int i = th.tid; i < S::JcmN; i += NT) L[S::t_Jcm + i] = L[S::Jcm0 + i];
     {
         real_t *Winv = L + S::bufA, *AiNc = L + S::bufN, *JbT = L + S::JbT;
         for (int lv = 0; lv < su.n_levels && st_task; lv++) {
@@ -691,9 +713,19 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
             real_t *Jt = L + S::t_Jt, *T1 = L + S::t_T1, *Lt = L + S::t_Lt, *Q = L + S::t_Q, *QW = L + S::t_QW, *Jkt = L + S::t_Jkt, *U = L + S::t_U;
             // --- J_task rows by link mode (dwbc.cpp:709-788)
             DWBC_SYNC();
+            // (two instantiations: a batch without a COM level runs the loop that knows none)
+            auto task_rows = [&](auto with_com) {
             int row = 0;
             for (int li = 0; li < su.t_nlinks[lv]; li++) {
                 const int mode = su.t_mode[lv][li], link = su.t_link[lv][li];
+                if constexpr (decltype(with_com)::value) {
+                    if (link == nb) {  // the COM link: jac_ = jac_com_, whatever frame the mode names (dwbc.cpp:352-353); no body of its own
+                        const int rsel = mode <= TASK_LINK_6D_CUSTOM_FRAME ? 0 : (mode <= TASK_LINK_POSITION_CUSTOM_FRAME ? 1 : 2);
+                        com_task_rows_rm<N, NT>(th, L + S::t_Jcm, Jt, row, rsel);
+                        row += rsel == 0 ? 6 : 3;
+                        continue;
+                    }
+                }
                 real_t pl[3] = {0, 0, 0};
                 if (mode == TASK_LINK_6D_COM_FRAME || mode == TASK_LINK_POSITION_COM_FRAME)
                     for (int a = 0; a < 3; a++) pl[a] = body[link * kBodyStride + BF_COM + a];
@@ -706,6 +738,8 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
                 else if (mode <= TASK_LINK_POSITION_CUSTOM_FRAME) { point_jacobian<N, NB, NT>(th, L + S::Rw, L + S::pw, L + S::aw, topo, nb, link, P, Jt, N, row, 3, 1); row += 3; }
                 else { point_jacobian<N, NB, NT>(th, L + S::Rw, L + S::pw, L + S::aw, topo, nb, link, P, Jt, N, row, 3, 2); row += 3; }
             }
+            };
+            if (su.has_com_task) task_rows(std::true_type{}); else task_rows(std::false_type{});
             DWBC_SYNC();
             // --- CalculateJKT (wbd.cpp:207-213)
             mmg<T, N, N, 0>(T1, N, Jt, N, AiNc, N, t, N, N);          // J_t A^-1 N_c
