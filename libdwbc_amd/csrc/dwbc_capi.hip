@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,7 +17,7 @@
 
 using namespace dwbc;
 
-extern "C" int dwbc_f32_lookup(int n, int nb, int nlv, int which, int lean, int topo, const void **fn, const void **fn_wide, int *lds_bytes, int *lds_bytes_wide, int *topo_out);
+extern "C" const dwbc_plan::Row *dwbc_f32_rows(int *count);  // launch table of the fp32 build (dwbc_kernels_f32.hip)
 
 // DWBC_F32 batches: the fp32 kernels (dwbc_kernels_f32.hip) work on the double buffers of the boundary; the model table is
 // converted to float once
@@ -112,14 +113,16 @@ int dwbc_model_get_arrays(const dwbc_model *mm, int32_t *parent, double *R_T, do
 //      generic (any tree of its size) or built for one parent table (TopoPack: the tree-sparse sweep); the latter is preferred
 //      when its table equals the model's
 namespace {
-struct KernelPack { void *dl; const KernelEntry *tab; int count; std::vector<int> parents; GcEntry gc; };  // parents empty: generic; gc.fn: the size's general-contact kernel or nullptr
+struct KernelPack { void *dl; dwbc_plan::Table tab; std::vector<int> parents; };  // parents empty: generic
 std::vector<KernelPack> g_packs;
 std::mutex g_pack_mutex;
-bool builtin_has(int n, int nb) {
-    for (const auto &k : kKernels)
-        if (k.n == n && k.nb == nb) return true;
+bool has_size(const dwbc_plan::Table &t, int n, int nb) {
+    for (int i = 0; i < t.count; i++)
+        if (t.rows[i].n == n && t.rows[i].nb == nb) return true;
     return false;
 }
+const dwbc_plan::Table kBuiltin{kRows, (int)(sizeof(kRows) / sizeof(kRows[0]))};
+bool builtin_has(int n, int nb) { return has_size(kBuiltin, n, nb); }
 std::vector<int> clean_parents(const Model &m) {
     std::vector<int> p(m.parent.size());
     for (size_t i = 0; i < p.size(); i++) p[i] = m.parent[i] < 0 ? 0 : m.parent[i];
@@ -131,27 +134,12 @@ unsigned tree_tag(const std::vector<int> &parents) {  // FNV-1a over the parents
         for (int b = 0; b < 4; b++) { h ^= (unsigned)((p >> (8 * b)) & 0xff); h *= 16777619u; }
     return h;
 }
-// nlv < 0: any level count.  tree: only a pack built for exactly these parents (or, generic = true, only a generic one)
-const KernelEntry *pack_lookup(int n, int nb, int nlv, const std::vector<int> &parents, bool generic) {
-    std::lock_guard<std::mutex> lk(g_pack_mutex);
-    for (const auto &p : g_packs) {
-        if (generic ? !p.parents.empty() : p.parents != parents) continue;
-        for (int i = 0; i < p.count; i++)
-            if (p.tab[i].n == n && p.tab[i].nb == nb && (nlv < 0 || p.tab[i].nlv == nlv)) return &p.tab[i];
-    }
-    return nullptr;
-}
-// the general-contact kernel of a model size: built in (TOCABI) or from a loaded pack of that size
-GcEntry find_gc(int n, int nb) {  // fn == nullptr: none
-    if (const GcEntry *g = lookup_gc(n, nb)) return *g;
+// the loaded pack of a model size built for exactly these parents (or, generic = true, for any tree); rows == nullptr: none
+dwbc_plan::Table pack_lookup(int n, int nb, const std::vector<int> &parents, bool generic) {
     std::lock_guard<std::mutex> lk(g_pack_mutex);
     for (const auto &p : g_packs)
-        if (p.gc.fn && p.gc.n == n && p.gc.nb == nb) return p.gc;
-    return GcEntry{0, 0, nullptr, 0, nullptr, 0};
-}
-const KernelEntry *pack_pick(int n, int nb, int nlv, const std::vector<int> &parents) {
-    if (const KernelEntry *ke = pack_lookup(n, nb, nlv, parents, false)) return ke;
-    return pack_lookup(n, nb, nlv, parents, true);
+        if ((generic ? p.parents.empty() : p.parents == parents) && has_size(p.tab, n, nb)) return p.tab;
+    return dwbc_plan::Table{nullptr, 0};
 }
 std::string lib_dir_impl() {
     Dl_info di;
@@ -166,25 +154,19 @@ std::string lib_dir_impl() {
 int try_load_pack(const std::string &path, const std::vector<int> &parents, bool want_tree, std::string &err) {
     void *dl = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
     if (!dl) return 0;
-    typedef const KernelEntry *(*table_fn)(int *, unsigned *);
+    typedef const dwbc_plan::Row *(*table_fn)(int *, unsigned *);
     typedef const int *(*parents_fn)(int *);
     table_fn tf = (table_fn)dlsym(dl, "dwbc_pack_table");
     parents_fn pf = (parents_fn)dlsym(dl, "dwbc_pack_parents");
     int count = 0;
     unsigned tag = 0;
-    const KernelEntry *tab = tf ? tf(&count, &tag) : nullptr;
+    const dwbc_plan::Row *tab = tf ? tf(&count, &tag) : nullptr;
     if (!tab || tag != kernel_abi_tag()) {
         dlclose(dl);
         err = path + " was built from another version of the kernels: rebuild it (make -C libdwbc_amd/csrc pack ...)";
         return -1;
     }
-    KernelPack kp{dl, tab, count, {}, GcEntry{0, 0, nullptr, 0}};
-    typedef const void *(*gc_fn)(int *);
-    if (gc_fn gf = (gc_fn)dlsym(dl, "dwbc_pack_gc")) {
-        int lds = 0;
-        const void *fn = gf(&lds);
-        if (fn && count > 0) kp.gc = GcEntry{tab[0].n, tab[0].nb, reinterpret_cast<void (*)(const Setup, const BatchIO)>(const_cast<void *>(fn)), lds, nullptr, 0};
-    }
+    KernelPack kp{dl, dwbc_plan::Table{tab, count}, {}};
     if (pf) {
         int pnb = 0;
         const int *pp = pf(&pnb);
@@ -203,7 +185,7 @@ bool ensure_kernels(const Model &m, std::string &err) {
     const int n = m.ndof, nb = m.nb;
     if (builtin_has(n, nb)) return true;
     const std::vector<int> parents = clean_parents(m);
-    if (pack_lookup(n, nb, -1, parents, false)) return true;
+    if (pack_lookup(n, nb, parents, false).rows) return true;
     char tagbuf[16];
     snprintf(tagbuf, sizeof tagbuf, "%08x", tree_tag(parents));
     const std::string base = "libdwbc_pack_" + std::to_string(n) + "_" + std::to_string(nb);
@@ -216,7 +198,7 @@ bool ensure_kernels(const Model &m, std::string &err) {
         if (r < 0) return false;
         if (r > 0) return true;
     }
-    if (pack_lookup(n, nb, -1, parents, true)) return true;
+    if (pack_lookup(n, nb, parents, true).rows) return true;
     for (const auto &d : dirs) {
         const std::string path = d + "/" + base + ".so";
         const int r = try_load_pack(path, parents, false, err);
@@ -229,6 +211,38 @@ bool ensure_kernels(const Model &m, std::string &err) {
     return false;
 }
 }  // namespace
+
+// what the planner (dwbc_launch_plan.h) needs to know of a batch; the environment switches are read here and nowhere else
+static dwbc_plan::Request plan_request(const dwbc_batch *b, bool reduced) {
+    dwbc_plan::Request q{};
+    q.n = b->n;
+    q.nb = b->su.nb;
+    q.levels = b->su.n_levels;
+    q.topo = b->su.topo_kind;
+    q.tree_match = b->tree_match;
+    q.arith = b->dtype == DWBC_F32 ? dwbc_plan::kFloat : dwbc_plan::kDouble;
+    q.B = b->B;
+    q.n_cu = b->n_cu;
+    q.reduced = reduced;
+    q.max_active = b->max_active;
+    q.wide_tasks = setup_wide_tasks(b->su);
+    q.hqp = b->hqp != 0;
+    q.warm = b->warm != 0;
+    q.n_traj = b->su.n_traj;
+    q.has_com_task = b->su.has_com_task != 0;
+    q.n_custom = b->su.n_custom;
+    q.dump_on = b->dump_on;
+    q.no_wide = getenv("DWBC_NO_WIDE") != nullptr;
+    q.no_pair = getenv("DWBC_NO_PAIR") != nullptr;
+    q.no_lean = getenv("DWBC_NO_LEAN") != nullptr;
+    q.pair_always = getenv("DWBC_PAIR_ALWAYS") != nullptr;
+    // which wave of a two-wave workgroup is the main one can be swapped per workgroup (bit of the workgroup index) to steer the main
+    // waves of a CU's four workgroups onto different SIMDs; measured at B = 1024 (profiles/r03e_pair_roles.txt): no swap 82.3 us per
+    // launch, bit 8 / bit 9 99 - 102 us (the dispatcher already spreads wave 0 of consecutive workgroups), so the default is no swap
+    const char *sb = getenv("DWBC_PAIR_SWAP_BIT");
+    q.pair_swap_bit = sb ? atoi(sb) : -1;
+    return q;
+}
 
 dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype) {
     if (!m || B < 1) { g_err = "bad arguments"; return nullptr; }
@@ -249,7 +263,16 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     b->dtype = dtype;
     b->n = m->m.ndof;
     b->m = b->n - 6;
-    b->kern = nullptr;  // picked at the first solve (pick_kernel: the level count is not known yet)
+    b->tables[b->n_tables++] = kBuiltin;
+    int n_f32 = 0;
+    const dwbc_plan::Row *f32 = dwbc_f32_rows(&n_f32);
+    b->tables[b->n_tables++] = dwbc_plan::Table{f32, n_f32};
+    for (const bool generic : {false, true}) {
+        const dwbc_plan::Table t = pack_lookup(b->n, m->m.nb, clean_parents(m->m), generic);
+        if (!t.rows) continue;
+        b->tables[b->n_tables++] = t;
+        b->tree_match = b->tree_match || !generic;
+    }
     b->dl = DumpLayout::make(b->n);
     setup_init(b->su, m->m.nb, b->n, m->m.maxdepth);
     auto bad = [&](const char *what, hipError_t e) {
@@ -259,6 +282,7 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     };
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return bad("hipSetDevice", e);
+    if ((e = hipDeviceGetAttribute(&b->n_cu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return bad("hipDeviceGetAttribute", e);
     std::vector<double> body;
     std::vector<int> topo;
     m->m.body_table(body);
@@ -478,7 +502,8 @@ int dwbc_batch_set_max_active_contacts(dwbc_batch *b, int n) {
     if (n == b->max_active) return 1;
     if (n > 2) {
         if (b->dtype == DWBC_F32) return fail("three active contacts: fp64 batches only");
-        if (!find_gc(b->n, b->su.nb).fn) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
+        const dwbc_plan::Request q = plan_request(b, false);
+        if (!dwbc_plan::Candidates(q, dwbc_plan::kGc, b->tables, b->n_tables).pick(dwbc_plan::kWideTasks, 0u)) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
     }
     if (!b->own_wrench) return fail("wrench is bound to a device buffer: set the contact capacity before binding");
     if (n < b->max_active) {  // lowering the capacity: the flags already set must fit it (they were validated against the old one)
@@ -598,107 +623,30 @@ static int upload_inputs(dwbc_batch *b) {
     return 1;
 }
 
-// the lean instantiation (EXTRAS = false) serves every launch that uses none of the optional paths
-static bool lean_ok(const dwbc_batch *b) {
-    return b->hqp && !b->warm && b->su.n_traj == 0 && !b->su.has_com_task && b->su.n_custom == 0 && !b->dump_on && !getenv("DWBC_NO_LEAN");
-}
-
-// dynamic LDS of one flavour of an entry: the lean capped build may be laid out on the compact map (Lds3)
-static int entry_lds(const KernelEntry *ke, void (*fn)(const Setup, const BatchIO)) {
-    return (fn == ke->fn_lean && ke->lds_bytes_lean) ? ke->lds_bytes_lean : ke->lds_bytes;
-}
-
-// the paired kernel serves the lean full-model cycle of small batches (one instance per SIMD); DWBC_NO_PAIR switches it off
-static bool pair_ok(const dwbc_batch *b, const KernelEntry *ke, bool wide, bool lean, bool reduced) {
-    return ke && ke->fn_pair && wide && lean && !reduced && b->dtype != DWBC_F32 && !getenv("DWBC_NO_PAIR");
-}
-
-static const KernelEntry *pick_kernel(const dwbc_batch *b, bool reduced) {
-    const int which = reduced ? 2 : 0;
-    if (const KernelEntry *ke = lookup_kernel(b->n, b->su.nb, b->su.n_levels, which, b->su.topo_kind)) return ke;
-    return reduced ? nullptr : pack_pick(b->n, b->su.nb, b->su.n_levels, clean_parents(b->model->m));  // packs hold the full-model cycle only
-}
-
-// fp32 launch: the fp32 kernels read and write the double buffers of the boundary themselves (io_t); only the model table is
-// kept in float
-static int launch_f32(dwbc_batch *b, bool reduced) {
-    const int which = reduced ? 2 : 0;
-    const int lean = lean_ok(b) ? 1 : 0;
-    const int key = ((which * 16 + b->su.n_levels) * 2 + lean) * 2 + (b->su.topo_kind ? 1 : 0);
-    if (key != b->f32_key) {
-        if (!dwbc_f32_lookup(b->n, b->su.nb, b->su.n_levels, which, lean, b->su.topo_kind, &b->f32_fn, &b->f32_fn_wide, &b->f32_lds, &b->f32_lds_wide, &b->f32_topo))
-            return fail("no fp32 kernel for this model / number of task levels");
-        HIP_OK(hipFuncSetAttribute(b->f32_fn, hipFuncAttributeMaxDynamicSharedMemorySize, b->f32_lds));
-        if (b->f32_fn_wide) HIP_OK(hipFuncSetAttribute(b->f32_fn_wide, hipFuncAttributeMaxDynamicSharedMemorySize, b->f32_lds_wide));
-        hipDeviceProp_t prop;
-        HIP_OK(hipGetDeviceProperties(&prop, b->device));
-        b->n_cu = prop.multiProcessorCount;
-        b->f32_key = key;
+// one launch of the cycle: the planner picks the build, whatever its arithmetic type or kind
+static int launch(dwbc_batch *b, bool reduced) {
+    const dwbc_plan::Plan p = dwbc_plan::plan(plan_request(b, reduced), b->tables, b->n_tables);
+    if (!p.row) return fail(p.err);
+    const void *fn = p.row->fn;
+    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        b->lds_attr_set.push_back(fn);
     }
-    if (b->dump_on) return fail("the dump record is not available on DWBC_F32 batches");
-    if (!b->f_body) {
+    // the fp32 kernels read and write the double buffers of the boundary themselves (io_t); only the model table is kept in float
+    const bool f32 = b->dtype == DWBC_F32;
+    if (f32 && !b->f_body) {
         std::vector<double> body;
         b->model->m.body_table(body);
         HIP_OK(hipMalloc(&b->f_body, body.size() * sizeof(float)));
         hipLaunchKernelGGL(dwbc_cvt_d2f, dim3((unsigned)((body.size() + 255) / 256)), dim3(256), 0, b->stream, b->d_body, b->f_body, body.size());
     }
-    struct IoF32 {  // BatchIO of the fp32 namespace: same members, real_t = float
-        int B;
-        const double *q, *qdot;
-        const unsigned char *flags;
-        const double *fstar, *traj, *ctime, *custom_J;
-        double *tau, *wrench;
-        int *status, *diag;
-        float *dump;
-        const float *body;
-        const int *topo;
-        int hqp, pair_swap_bit, warm, wrench_ld;
-    } io{};
-    static_assert(sizeof(IoF32) == sizeof(BatchIO), "BatchIO layouts of the two builds must match");
+    BatchIO io{};
     io.B = b->B;
     io.q = b->d_q;
     io.qdot = b->d_qdot;
     io.traj = b->su.n_traj > 0 ? b->d_traj : nullptr;
     io.ctime = b->d_ctime;
     io.custom_J = b->su.n_custom > 0 ? b->d_custom : nullptr;
-    io.flags = b->d_flags;
-    io.fstar = b->d_fstar;
-    io.tau = b->d_tau;
-    io.wrench = b->d_wrench;
-    io.status = b->d_status;
-    io.diag = b->d_diag;
-    io.dump = nullptr;
-    io.body = b->f_body;
-    io.topo = b->d_topo;
-    io.hqp = b->hqp;
-    io.pair_swap_bit = -1;
-    io.warm = (b->warm && b->ws_valid) ? 1 : 0;
-    b->ws_valid = !lean;  // the full build leaves every QP's working set in the diagnostics record
-    const bool wide = b->f32_fn_wide && b->B <= 4 * b->n_cu && !getenv("DWBC_NO_WIDE");
-    void *args[] = {(void *)&b->su, (void *)&io};
-    HIP_OK(hipLaunchKernel(wide ? b->f32_fn_wide : b->f32_fn, dim3(b->B), dim3(kNT), args, wide ? b->f32_lds_wide : b->f32_lds, b->stream));
-    return 1;
-}
-
-// three active contacts, or a task level of more than six dof: every instance of the batch goes through the general-contact kernel
-// (lean scope: link tasks and the synthetic COM link); its TG = 12 instantiation when a level is wider than six
-static int launch_gc(dwbc_batch *b) {
-    const GcEntry gc_ = find_gc(b->n, b->su.nb), *g = &gc_;
-    const bool wide_tasks = setup_wide_tasks(b->su);
-    if (!g->fn) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
-    if (wide_tasks && !g->fn_wide_tasks) return fail("task levels of more than 6 dof: built in for TOCABI's size only");
-    if (!b->hqp) return fail("three active contacts / task levels of more than 6 dof: hqp = true only (the reference's closed-form redistribution is written for two contacts, src/dwbc.cpp:1570-1619)");
-    if (b->su.n_traj > 0 || b->su.n_custom > 0 || b->dump_on)
-        return fail("three active contacts / task levels of more than 6 dof: link and COM tasks with f* from SetTaskSpace only (no trajectories, no TASK_CUSTOM levels, no dump record)");
-    auto fn = wide_tasks ? g->fn_wide_tasks : g->fn;
-    const int lds_bytes = wide_tasks ? g->lds_bytes_wide_tasks : g->lds_bytes;
-    if (b->gc_attr_set != (wide_tasks ? 2 : 1)) {
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        b->gc_attr_set = wide_tasks ? 2 : 1;
-    }
-    BatchIO io{};
-    io.B = b->B;
-    io.q = b->d_q;
     io.flags = b->d_flags;
     io.fstar = b->d_fstar;
     io.tau = b->d_tau;
@@ -706,72 +654,16 @@ static int launch_gc(dwbc_batch *b) {
     io.wrench_ld = 6 * b->max_active;
     io.status = b->d_status;
     io.diag = b->d_diag;
-    io.body = b->d_body;
-    io.topo = b->d_topo;
-    io.hqp = 1;
-    b->ws_valid = false;  // cold-started QPs, no working sets kept
-    hipLaunchKernelGGL(fn, dim3(b->B), dim3(kNT), lds_bytes, b->stream, b->su, io);
-    return hipGetLastError() == hipSuccess ? 1 : fail("general-contact kernel launch failed");
-}
-
-static int launch(dwbc_batch *b, bool reduced = false) {
-    if (b->max_active > 2 || setup_wide_tasks(b->su)) {
-        if (reduced) return fail("three active contacts / task levels of more than 6 dof: not built on the reduced dynamics path");
-        if (b->dtype == DWBC_F32) return fail("three active contacts / task levels of more than 6 dof: fp64 batches only");
-        return launch_gc(b);
-    }
-    if (b->dtype == DWBC_F32) return launch_f32(b, reduced);
-    const KernelEntry *ke = pick_kernel(b, reduced);
-    if (!ke) return fail("no kernel for this model / number of task levels");
-    if (ke != b->kern) {
-        b->kern = ke;
-        b->attr_set = false;
-    }
-    BatchIO io{};
-    io.B = b->B;
-    io.q = b->d_q;
-    io.qdot = b->d_qdot;
-    io.traj = b->su.n_traj > 0 ? b->d_traj : nullptr;
-    io.ctime = b->d_ctime;
-    io.custom_J = b->su.n_custom > 0 ? b->d_custom : nullptr;
-    io.flags = b->d_flags;
-    io.fstar = b->d_fstar;
-    io.tau = b->d_tau;
-    io.wrench = b->d_wrench;
-    io.status = b->d_status;
-    io.diag = b->d_diag;
-    io.dump = b->dump_on ? b->d_dump : nullptr;
-    io.body = b->d_body;
+    io.dump = b->dump_on ? b->d_dump : nullptr;  // (never on an fp32 batch: the planner refuses it)
+    io.body = f32 ? reinterpret_cast<const double *>(b->f_body) : b->d_body;  // real_t of the build that p.row belongs to
     io.topo = b->d_topo;
     io.hqp = b->hqp;
+    io.pair_swap_bit = p.pair_swap_bit;
     io.warm = (b->warm && b->ws_valid) ? 1 : 0;
-    if (!b->attr_set) {
-        for (auto fn : {b->kern->fn, b->kern->fn_wide, b->kern->fn_lean, b->kern->fn_wide_lean})
-            if (fn) HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, entry_lds(b->kern, fn)));
-        if (b->kern->fn_pair)
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(b->kern->fn_pair), hipFuncAttributeMaxDynamicSharedMemorySize, b->kern->lds_bytes_pair));
-        hipDeviceProp_t prop;
-        HIP_OK(hipGetDeviceProperties(&prop, b->device));
-        b->n_cu = prop.multiProcessorCount;
-        b->attr_set = true;
-    }
-    const bool wide = b->kern->fn_wide && b->B <= 4 * b->n_cu && !getenv("DWBC_NO_WIDE");
-    const bool lean = b->kern->fn_lean && lean_ok(b);
-    b->ws_valid = !lean && !reduced;  // the full build leaves every QP's working set in the diagnostics record (DG_QP_ACT)
-    // (DWBC_PAIR_ALWAYS=1: development switch, the two-wave kernel at any batch size)
-    if (pair_ok(b, b->kern, wide || getenv("DWBC_PAIR_ALWAYS"), lean, reduced)) {
-        // two waves per instance, side chains on the helper wave (dwbc_cycle2p.h).  Which wave of a workgroup is the main one can be
-        // swapped per workgroup (DWBC_PAIR_SWAP_BIT = bit of the workgroup index) to steer the main waves of a CU's four workgroups
-        // onto different SIMDs; measured at B = 1024 (profiles/r03e_pair_roles.txt): no swap 82.3 us per launch, bit 8 / bit 9 99 - 102 us
-        // (the dispatcher already spreads wave 0 of consecutive workgroups), so the default is no swap.
-        const char *sb = getenv("DWBC_PAIR_SWAP_BIT");
-        io.pair_swap_bit = sb ? atoi(sb) : -1;
-        hipLaunchKernelGGL(b->kern->fn_pair, dim3(b->B), dim3(2 * kNT), b->kern->lds_bytes_pair, b->stream, b->su, io);
-        return hipGetLastError() == hipSuccess ? 1 : fail("paired kernel launch failed");
-    }
-    auto fn = wide ? (lean ? b->kern->fn_wide_lean : b->kern->fn_wide) : (lean ? b->kern->fn_lean : b->kern->fn);
-    hipLaunchKernelGGL(fn, dim3(b->B), dim3(kNT), entry_lds(b->kern, fn), b->stream, b->su, io);
-    HIP_OK(hipGetLastError());
+    void *args[] = {(void *)&b->su, (void *)&io};
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    b->ws_valid = p.ws_valid_after;
+    b->last = p;
     return 1;
 }
 
@@ -993,58 +885,23 @@ int dwbc_batch_get(dwbc_batch *b, int field, void *out, size_t bytes) {
     return 1;
 }
 
+// the plan of the last accepted launch; before any solve, the one a full-model solve of the batch as it stands would get
+static dwbc_plan::Plan report_plan(const dwbc_batch *b) {
+    return b->last.row ? b->last : dwbc_plan::plan(plan_request(b, false), b->tables, b->n_tables);
+}
+
 const char *dwbc_batch_kernel_name(const dwbc_batch *b) {
-    static thread_local std::string name;
-    if (b->max_active > 2 || setup_wide_tasks(b->su)) {
-        name = "dwbc::dwbc_cycle_kernel_gc<" + std::to_string(b->n) + ", " + std::to_string(b->su.nb) + ", 64, " + (setup_wide_tasks(b->su) ? "12" : "6") + ">";
-        return name.c_str();
-    }
-    const KernelEntry *ke = pick_kernel(b, b->last_reduced);
-    const std::string pre = b->dtype == DWBC_F32 ? "dwbc_f32::" : "dwbc::";  // as rocprofv3 prints the instantiations
-    if (!ke) return "";
-    const std::string topo = ", " + pre + (ke->topo == 1 ? "TopoTocabi" : (ke->topo == 2 ? "TopoPack" : "TopoGeneric"));
-    const std::string sz = std::to_string(ke->n) + ", " + std::to_string(ke->nb);
-    if (b->last_reduced) {
-        name = pre + "dwbc_cycle_kernel_reduced<" + sz + ", " + std::to_string(ke->nlv) + ", 64" + topo + ">";
-        return name.c_str();
-    }
-    int n_cu = b->n_cu;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, b->device) == hipSuccess) n_cu = prop.multiProcessorCount;
-    }
-    const bool wide = ke->fn_wide && b->B <= 4 * n_cu && !getenv("DWBC_NO_WIDE");
-    if (pair_ok(b, ke, wide, ke->fn_lean && lean_ok(b), false)) {
-        name = pre + "dwbc_cycle_kernel_v2p<" + sz + ", " + std::to_string(ke->nlv) + topo + ">";
-        return name.c_str();
-    }
-    name = pre + (wide ? "dwbc_cycle_kernel_v2w<" : "dwbc_cycle_kernel_v2<") + sz + ", " + std::to_string(ke->nlv) + ", 64" +
-           (ke->fn_lean && lean_ok(b) ? ", false" : ", true") + topo + ((!wide && ke->fn_lean && lean_ok(b) && ke->lds_bytes_lean) ? ", true" : "") + ">";
-    return name.c_str();
+    static thread_local char name[160];  // as rocprofv3 prints the instantiation
+    const dwbc_plan::Plan p = report_plan(b);
+    if (!p.row) return "";
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
 }
 
 int dwbc_batch_launch_info(const dwbc_batch *b, int *threads, int *lds) {
-    if (b->max_active > 2 || setup_wide_tasks(b->su)) {
-        const GcEntry g = find_gc(b->n, b->su.nb);
-        if (threads) *threads = kNT;
-        if (lds) *lds = setup_wide_tasks(b->su) ? g.lds_bytes_wide_tasks : (g.fn ? g.lds_bytes : 0);
-        return 1;
-    }
-    const KernelEntry *ke = pick_kernel(b, b->last_reduced);
-    if (threads) *threads = kNT;
-    int n_cu = b->n_cu;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, b->device) == hipSuccess) n_cu = prop.multiProcessorCount;
-    }
-    const bool wide = ke && ke->fn_wide && b->B <= 4 * n_cu && !getenv("DWBC_NO_WIDE");
-    const bool compact = ke && !wide && !b->last_reduced && ke->fn_lean && lean_ok(b) && ke->lds_bytes_lean;
-    if (pair_ok(b, ke, wide, ke && ke->fn_lean && lean_ok(b), b->last_reduced)) {
-        if (threads) *threads = 2 * kNT;
-        if (lds) *lds = ke->lds_bytes_pair;
-        return 1;
-    }
-    if (lds) *lds = b->dtype == DWBC_F32 && b->f32_lds ? (wide ? b->f32_lds_wide : b->f32_lds) : (ke ? (compact ? ke->lds_bytes_lean : ke->lds_bytes) : 0);
+    const dwbc_plan::Plan p = report_plan(b);
+    if (threads) *threads = p.row ? p.threads : kNT;
+    if (lds) *lds = p.row ? p.lds : 0;
     return 1;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dwbc_batch.h"
+#include "dwbc_launch_plan.h"
 #include "dwbc_model.h"
 #include "dwbc_types.h"
 
@@ -33,7 +34,6 @@ struct PinnedAlloc {
 };
 template <class T>
 using PinnedVec = std::vector<T, PinnedAlloc<T>>;
-struct KernelEntry;
 std::string &capi_err();  // thread-local last error (dwbc_last_error)
 inline int capi_fail(const std::string &s) {
     capi_err() = s;
@@ -54,7 +54,6 @@ struct dwbc_batch {
     const dwbc_model *model = nullptr;
     int B = 0, device = 0, n = 0, m = 0;
     dwbc::Setup su{};
-    const dwbc::KernelEntry *kern = nullptr;
     hipStream_t stream = nullptr;
     // device buffers (owned unless bound)
     double *d_qdot = nullptr;  // B x n, allocated when the caller passes a qdot
@@ -75,13 +74,17 @@ struct dwbc_batch {
     int dtype = 0;  // DWBC_F64 | DWBC_F32 (arithmetic type of the kernels; the boundary buffers are always double)
     float *f_body = nullptr;
     int max_active = 2;           // simultaneously active contacts per instance the batch solves (2: product kernels; 3: dwbc_cycle_gc.h)
-    int gc_attr_set = 0;  // 1: the general-contact kernel's LDS attribute is set, 2: its wide-task instantiation's
-    const void *f32_fn = nullptr, *f32_fn_wide = nullptr;
-    int f32_lds = 0, f32_lds_wide = 0, f32_key = -1, f32_topo = 0;
     int hqp = 1;
     int warm = 0;           // last solve flags had DWBC_SOLVE_INIT clear
     bool ws_valid = false;  // diag holds the working sets of a full-build launch
-    bool last_reduced = false;  // mode of the most recent dwbc_batch_solve (kernel_name / launch_info report it)
+    bool last_reduced = false;  // mode of the most recent dwbc_batch_solve (the LQP / JACC entry points need the matching cycle)
+    // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32), then the loaded pack of the
+    // model's own tree, then the generic pack of its size -- resolved once, at creation
+    dwbc_plan::Table tables[4] = {};
+    int n_tables = 0;
+    bool tree_match = false;  // tables[] holds a pack compiled for this model's parent table
+    dwbc_plan::Plan last{};   // plan of the last accepted launch (row == nullptr: none yet): kernel_name / launch_info report it
+    std::vector<const void *> lds_attr_set;  // kernels whose dynamic-LDS attribute has been raised on this batch's device
     // host mirrors of the inputs
     dwbc::PinnedVec<double> h_q, h_fstar;
     dwbc::PinnedVec<unsigned char> h_flags;
@@ -99,8 +102,7 @@ struct dwbc_batch {
     // host-to-device copies of a solve and waited for before anything rewrites a mirror (dwbc_batch_set_*, dwbc_batch_host_ptr)
     hipEvent_t ev_upload = nullptr;
     bool upload_pending = false;
-    bool attr_set = false;
-    int n_cu = 0;
+    int n_cu = 0;  // compute units of the batch's device
     dwbc::DumpLayout dl{};
 };
 

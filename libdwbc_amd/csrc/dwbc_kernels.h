@@ -1,9 +1,12 @@
 // dwbc_kernels.h -- __global__ entry points of the fused cycle and the table of instantiations.  Included by dwbc_capi.hip
 // (DWBC_REAL = double, the product path) and by dwbc_kernels_f32.hip (DWBC_REAL = float with the namespace renamed to
-// dwbc_f32): the same source in both arithmetic types, looked up at run time through KernelEntry.
+// dwbc_f32): the same source in both arithmetic types, each emitting its rows of the launch table (dwbc_launch_plan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
+#include "dwbc_launch_plan.h"
 #include "dwbc_reduced.h"
 #include "dwbc_cycle2p.h"
 #include "dwbc_cycle_gc.h"
@@ -81,103 +84,69 @@ __global__ __launch_bounds__(NT) void dwbc_cycle_kernel_reduced(const Setup su, 
     cycle_instance_reduced<N, NB, NLV, NT, Topo>(th, su, io, inst, lds, iL);
 }
 
-constexpr int kNT = 64;
-// the paired kernel exists in the fp64 build, for one and two task levels (three levels no longer fit four workgroups per CU)
-#ifdef DWBC_NO_PAIR_KERNEL
-#define DWBC_PAIR_ENTRY(NLV) nullptr, 0
-#else
-#define DWBC_PAIR_ENTRY(NLV) dwbc_cycle_kernel_v2p<39, 34, NLV, TopoTocabi>, Lds4<39, 34, NLV>::total_bytes
-#endif
+#define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
+constexpr int kNT = DWBC_NT;
+static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
+// dwbc_capi.hip fills one BatchIO for the kernels of both arithmetic types: the members that differ are pointers
+static_assert(sizeof(BatchIO) == 8 + 14 * sizeof(void *) + 4 * sizeof(int) && offsetof(BatchIO, body) == 8 + 12 * sizeof(void *),
+              "BatchIO layouts of the two builds must match");
 
-struct KernelEntry {
-    int n, nb, nlv;  // nlv = task levels the LDS map is sized for (0: any)
-    int topo;        // Setup::topo_kind the instantiation was built for (1: TopoTocabi's constant tree); 0 = any tree
-    void (*fn)(const Setup, const BatchIO);
-    int lds_bytes;
-    void (*fn_wide)(const Setup, const BatchIO);  // uncapped-register build for batches of at most 4 instances per CU
-    void (*fn_lean)(const Setup, const BatchIO);       // the same two without the optional paths (EXTRAS = false), or nullptr
-    void (*fn_wide_lean)(const Setup, const BatchIO);
-    int lds_bytes_lean;  // dynamic LDS of fn_lean when it differs from lds_bytes (the compact map), else 0
-    void (*fn_pair)(const Setup, const BatchIO);  // two waves per instance (128 threads), lean, batches of at most 4 instances per CU; or nullptr
-    int lds_bytes_pair;
-};
-// the general-contact kernel of a model size (any tree, any number of levels): one per (n, nb)
-struct GcEntry {
-    int n, nb;
-    void (*fn)(const Setup, const BatchIO);
-    int lds_bytes;
-    void (*fn_wide_tasks)(const Setup, const BatchIO);  // task levels of up to kMaxTaskDofWide dof, or nullptr
-    int lds_bytes_wide_tasks;
-};
-// instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four
-// flavours use the constant tree; any other 34-body tree runs the TopoGeneric build (full flavour only).  Other model sizes come
-// from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
-#if !defined(DWBC_PACK_N) && !defined(DWBC_NO_PAIR_KERNEL)
-const GcEntry kKernelsGc[] = {
-    {39, 34, dwbc_cycle_kernel_gc<39, 34, kNT>, LdsG<39, 34, kGcContacts>::total_bytes,
-     dwbc_cycle_kernel_gc<39, 34, kNT, kMaxTaskDofWide>, LdsG<39, 34, kGcContacts, kMaxTaskDofWide>::total_bytes},
-};
-inline const GcEntry *lookup_gc(int n, int nb) {
-    for (const GcEntry &e : kKernelsGc)
-        if (e.n == n && e.nb == nb) return &e;
-    return nullptr;
-}
-#endif
-#ifdef DWBC_PACK_N
-#elif defined(DWBC_EXPERIMENT)
-// A/B build (make experiment VARIANT=.. XFLAGS=..): only the BASELINE config[1] instantiation, seconds to compile
-const KernelEntry kKernels[] = {
-    {39, 34, 2, 1, dwbc_cycle_kernel_v2<39, 34, 2, kNT, true, TopoTocabi>, Lds2<39, 34, 2>::total_bytes, dwbc_cycle_kernel_v2w<39, 34, 2, kNT, true, TopoTocabi>,
-     dwbc_cycle_kernel_v2<39, 34, 2, kNT, false, TopoTocabi, true>, dwbc_cycle_kernel_v2w<39, 34, 2, kNT, false, TopoTocabi>, Lds3<39, 34, 2>::total_bytes,
-     DWBC_PAIR_ENTRY(2)},
-};
-const KernelEntry kKernelsReduced[] = {
-    {39, 34, 2, 1, dwbc_cycle_kernel_reduced<39, 34, 2, kNT, TopoTocabi>, LdsR<39, 34, 2>::total_bytes, nullptr, nullptr, nullptr},
-};
+// ---- the launch table (dwbc_launch_plan.h): one row per launchable kernel.  DWBC_ROW instantiates KERNEL<template arguments> and
+// spells the same tokens into the row's name, so the name reported for a launch is the kernel's own (the fp32 build's rename of
+// `dwbc` reaches both).  A defaulted COMPACT = false is left out, as the names always were.
+namespace lp = dwbc_plan;
+#define DWBC_STR_(...) #__VA_ARGS__
+#define DWBC_STR(...) DWBC_STR_(__VA_ARGS__)
+#define DWBC_ROW(N, NB, NLV, TOPO_KIND, KIND, FLAVOUR, LDS, THREADS, KERNEL, ...)                                           \
+    lp::Row{N, NB, NLV, TOPO_KIND, kF32 ? lp::kFloat : lp::kDouble, lp::KIND, FLAVOUR,                                      \
+            reinterpret_cast<const void *>(&dwbc::KERNEL<__VA_ARGS__>), (int)LDS, THREADS, DWBC_STR(dwbc::KERNEL), DWBC_STR(__VA_ARGS__)}
+// capped extras, wide extras and wide lean build of one model size, level count and tree (TK: Row::topo of TOPO); the capped lean
+// build is laid out on the compact map (Lds3) for TOCABI's tree and on Lds2 in the packs
+#define DWBC_ROWS_V2(N, NB, NLV, TOPO, TK)                                                                                                       \
+    DWBC_ROW(N, NB, NLV, TK, kCycle, 0u, (Lds2<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2, N, NB, NLV, DWBC_NT, true, dwbc::TOPO),       \
+    DWBC_ROW(N, NB, NLV, TK, kCycle, lp::kWide, (Lds2<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2w, N, NB, NLV, DWBC_NT, true, dwbc::TOPO), \
+    DWBC_ROW(N, NB, NLV, TK, kCycle, lp::kWide | lp::kLean, (Lds2<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2w, N, NB, NLV, DWBC_NT, false, dwbc::TOPO),
+#define DWBC_ROW_LEAN(N, NB, NLV, TOPO, TK) \
+    DWBC_ROW(N, NB, NLV, TK, kCycle, lp::kLean, (Lds2<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2, N, NB, NLV, DWBC_NT, false, dwbc::TOPO),
+#define DWBC_ROW_LEAN_COMPACT(N, NB, NLV, TOPO, TK) \
+    DWBC_ROW(N, NB, NLV, TK, kCycle, lp::kLean | lp::kCompact, (Lds3<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2, N, NB, NLV, DWBC_NT, false, dwbc::TOPO, true),
+#define DWBC_ROW_REDUCED(N, NB, NLV, TOPO, TK) \
+    DWBC_ROW(N, NB, NLV, TK, kReduced, 0u, (LdsR<N, NB, NLV>::total_bytes), kNT, dwbc_cycle_kernel_reduced, N, NB, NLV, DWBC_NT, dwbc::TOPO),
+// any tree, any number of levels.  DWBC_NO_GC_KERNEL: a build without the general-contact kernel (fp32)
+#ifdef DWBC_NO_GC_KERNEL
+#define DWBC_ROW_GC(N, NB, TG, FLAVOUR)
 #else
-const KernelEntry kKernels[] = {
-    {39, 34, 1, 1, dwbc_cycle_kernel_v2<39, 34, 1, kNT, true, TopoTocabi>, Lds2<39, 34, 1>::total_bytes, dwbc_cycle_kernel_v2w<39, 34, 1, kNT, true, TopoTocabi>,
-     dwbc_cycle_kernel_v2<39, 34, 1, kNT, false, TopoTocabi, true>, dwbc_cycle_kernel_v2w<39, 34, 1, kNT, false, TopoTocabi>, Lds3<39, 34, 1>::total_bytes,
-     DWBC_PAIR_ENTRY(1)},
-    {39, 34, 2, 1, dwbc_cycle_kernel_v2<39, 34, 2, kNT, true, TopoTocabi>, Lds2<39, 34, 2>::total_bytes, dwbc_cycle_kernel_v2w<39, 34, 2, kNT, true, TopoTocabi>,
-     dwbc_cycle_kernel_v2<39, 34, 2, kNT, false, TopoTocabi, true>, dwbc_cycle_kernel_v2w<39, 34, 2, kNT, false, TopoTocabi>, Lds3<39, 34, 2>::total_bytes,
-     DWBC_PAIR_ENTRY(2)},
-    {39, 34, 3, 1, dwbc_cycle_kernel_v2<39, 34, 3, kNT, true, TopoTocabi>, Lds2<39, 34, 3>::total_bytes, dwbc_cycle_kernel_v2w<39, 34, 3, kNT, true, TopoTocabi>,
-     dwbc_cycle_kernel_v2<39, 34, 3, kNT, false, TopoTocabi, true>, dwbc_cycle_kernel_v2w<39, 34, 3, kNT, false, TopoTocabi>, Lds3<39, 34, 3>::total_bytes},
-    {39, 34, 4, 1, dwbc_cycle_kernel_v2<39, 34, 4, kNT, true, TopoTocabi>, Lds2<39, 34, 4>::total_bytes, dwbc_cycle_kernel_v2w<39, 34, 4, kNT, true, TopoTocabi>,
-     dwbc_cycle_kernel_v2<39, 34, 4, kNT, false, TopoTocabi, true>, dwbc_cycle_kernel_v2w<39, 34, 4, kNT, false, TopoTocabi>, Lds3<39, 34, 4>::total_bytes},
-    {39, 34, 1, 0, dwbc_cycle_kernel_v2<39, 34, 1, kNT, true, TopoGeneric>, Lds2<39, 34, 1>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 2, 0, dwbc_cycle_kernel_v2<39, 34, 2, kNT, true, TopoGeneric>, Lds2<39, 34, 2>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 3, 0, dwbc_cycle_kernel_v2<39, 34, 3, kNT, true, TopoGeneric>, Lds2<39, 34, 3>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 4, 0, dwbc_cycle_kernel_v2<39, 34, 4, kNT, true, TopoGeneric>, Lds2<39, 34, 4>::total_bytes, nullptr, nullptr, nullptr},
-};
-const KernelEntry kKernelsReduced[] = {
-    {39, 34, 1, 1, dwbc_cycle_kernel_reduced<39, 34, 1, kNT, TopoTocabi>, LdsR<39, 34, 1>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 2, 1, dwbc_cycle_kernel_reduced<39, 34, 2, kNT, TopoTocabi>, LdsR<39, 34, 2>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 3, 1, dwbc_cycle_kernel_reduced<39, 34, 3, kNT, TopoTocabi>, LdsR<39, 34, 3>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 4, 1, dwbc_cycle_kernel_reduced<39, 34, 4, kNT, TopoTocabi>, LdsR<39, 34, 4>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 1, 0, dwbc_cycle_kernel_reduced<39, 34, 1, kNT, TopoGeneric>, LdsR<39, 34, 1>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 2, 0, dwbc_cycle_kernel_reduced<39, 34, 2, kNT, TopoGeneric>, LdsR<39, 34, 2>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 3, 0, dwbc_cycle_kernel_reduced<39, 34, 3, kNT, TopoGeneric>, LdsR<39, 34, 3>::total_bytes, nullptr, nullptr, nullptr},
-    {39, 34, 4, 0, dwbc_cycle_kernel_reduced<39, 34, 4, kNT, TopoGeneric>, LdsR<39, 34, 4>::total_bytes, nullptr, nullptr, nullptr},
-};
+#define DWBC_ROW_GC(N, NB, TG, FLAVOUR) \
+    DWBC_ROW(N, NB, 0, 0, kGc, FLAVOUR, (LdsG<N, NB, kGcContacts, TG>::total_bytes), kNT, dwbc_cycle_kernel_gc, N, NB, DWBC_NT, TG),
 #endif
+// the two-wave kernel exists in the fp64 build (DWBC_NO_PAIR_KERNEL: fp32), for one and two task levels (three levels no longer fit
+// four workgroups per CU)
+#ifdef DWBC_NO_PAIR_KERNEL
+#define DWBC_ROW_PAIR(NLV)
+#else
+#define DWBC_ROW_PAIR(NLV) \
+    DWBC_ROW(39, 34, NLV, 1, kCycle, lp::kLean | lp::kTwoWave, (Lds4<39, 34, NLV>::total_bytes), 2 * kNT, dwbc_cycle_kernel_v2p, 39, 34, NLV, dwbc::TopoTocabi),
+#endif
+// instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
+// and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
+// model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
+#define DWBC_ROWS_TOCABI_TREE(NLV) \
+    DWBC_ROWS_V2(39, 34, NLV, TopoTocabi, 1) DWBC_ROW_LEAN_COMPACT(39, 34, NLV, TopoTocabi, 1) DWBC_ROW_REDUCED(39, 34, NLV, TopoTocabi, 1)
+#define DWBC_ROWS_TOCABI_ANY(NLV) \
+    DWBC_ROW(39, 34, NLV, 0, kCycle, 0u, (Lds2<39, 34, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2, 39, 34, NLV, DWBC_NT, true, dwbc::TopoGeneric), \
+    DWBC_ROW_REDUCED(39, 34, NLV, TopoGeneric, 0)
 #ifndef DWBC_PACK_N
-// which: 0 = full-model kernel, 2 = reduced dynamics
-// topo: Setup::topo_kind of the loaded model -- an instantiation for that constant tree is preferred, else the generic one
-inline const KernelEntry *lookup_kernel(int n, int nb, int nlv, int which, int topo) {
-    for (int pass = 0; pass < 2; pass++) {
-        const int want = pass == 0 ? topo : 0;
-        if (which == 2) {
-            for (const auto &k : kKernelsReduced)
-                if (k.n == n && k.nb == nb && k.nlv == nlv && k.topo == want) return &k;
-        } else {
-            for (const auto &k : kKernels)
-                if (k.n == n && k.nb == nb && k.nlv == nlv && k.topo == want) return &k;
-        }
-    }
-    return nullptr;
-}
+const lp::Row kRows[] = {
+#ifdef DWBC_EXPERIMENT
+    // A/B build (make experiment VARIANT=.. XFLAGS=..): only the BASELINE config[1] instantiations, seconds to compile
+    DWBC_ROWS_TOCABI_TREE(2) DWBC_ROW_PAIR(2)
+#else
+    DWBC_ROWS_TOCABI_TREE(1) DWBC_ROWS_TOCABI_TREE(2) DWBC_ROWS_TOCABI_TREE(3) DWBC_ROWS_TOCABI_TREE(4)
+    DWBC_ROW_PAIR(1) DWBC_ROW_PAIR(2)
+    DWBC_ROWS_TOCABI_ANY(1) DWBC_ROWS_TOCABI_ANY(2) DWBC_ROWS_TOCABI_ANY(3) DWBC_ROWS_TOCABI_ANY(4)
+#endif
+    DWBC_ROW_GC(39, 34, 6, 0u) DWBC_ROW_GC(39, 34, 12, lp::kWideTasks)
+};
 #endif
 
 // what a pack and the library that loads it must agree on (both are built from this header): the sizes of the shared structures
@@ -185,6 +154,6 @@ inline const KernelEntry *lookup_kernel(int n, int nb, int nlv, int which, int t
 #ifndef DWBC_SRC_HASH
 #define DWBC_SRC_HASH 0u
 #endif
-inline unsigned kernel_abi_tag() { return (unsigned)(DWBC_SRC_HASH) ^ (unsigned)(sizeof(Setup) * 2654435761u) ^ (unsigned)(sizeof(BatchIO) * 40503u) ^ (unsigned)(DG_COUNT * 97u) ^ (unsigned)sizeof(KernelEntry); }
+inline unsigned kernel_abi_tag() { return (unsigned)(DWBC_SRC_HASH) ^ (unsigned)(sizeof(Setup) * 2654435761u) ^ (unsigned)(sizeof(BatchIO) * 40503u) ^ (unsigned)(DG_COUNT * 97u) ^ (unsigned)sizeof(lp::Row); }
 
 }  // namespace dwbc

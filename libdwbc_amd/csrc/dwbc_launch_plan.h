@@ -1,0 +1,141 @@
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve: the table row of every launchable kernel and the one
+// function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
+// dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
+// The namespace is not `dwbc`: the fp32 build renames that one.
+#pragma once
+#include <cstdio>
+
+namespace dwbc_plan {
+
+enum Arith { kDouble = 0, kFloat = 1 };
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2 };  // full-model cycle, reduced (centroidal) dynamics, general-contact cycle
+enum : unsigned {
+    kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
+    kLean = 2,       // EXTRAS = false: none of the optional paths
+    kCompact = 4,    // the 20 KB LDS map (Lds3)
+    kTwoWave = 8,    // two wavefronts per instance (dwbc_cycle2p.h)
+    kWideTasks = 16  // general-contact cycle sized for task levels of up to 12 dof (TG = 12)
+};
+
+struct Row {  // one launchable kernel
+    int n, nb;  // model size (system dof, bodies)
+    int nlv;    // task levels its LDS map is sized for (0: any)
+    int topo;   // 0: any tree, 1: TopoTocabi's constant tree, 2: the one tree a pack was compiled for (TopoPack)
+    int arith, kind;
+    unsigned flavour;
+    const void *fn;
+    int lds;      // dynamic LDS bytes of fn
+    int threads;  // per instance (= per workgroup)
+    const char *base, *tail;  // base<tail> is the name a profiler prints for fn
+};
+struct Table {
+    const Row *rows;
+    int count;
+};
+
+struct Request {
+    int n, nb, levels;
+    int topo;         // Setup::topo_kind of the model
+    bool tree_match;  // the model's parent table is the one the offered TopoPack rows were compiled for
+    int arith, B, n_cu;
+    bool reduced;
+    int max_active;   // simultaneously active contacts the batch is set up for
+    bool wide_tasks;  // a task level of more than six dof
+    // what the lean build cannot serve
+    bool hqp, warm;
+    int n_traj;
+    bool has_com_task;
+    int n_custom;
+    bool dump_on;
+    // environment: DWBC_NO_WIDE, DWBC_NO_PAIR, DWBC_NO_LEAN, DWBC_PAIR_ALWAYS (development: the two-wave kernel at any batch size),
+    // DWBC_PAIR_SWAP_BIT (-1: unset)
+    bool no_wide, no_pair, no_lean, pair_always;
+    int pair_swap_bit;
+};
+
+struct Plan {
+    const Row *row;  // nullptr: refused, err says why
+    int threads, lds;
+    bool ws_valid_after;  // the launch leaves every QP's working set in the diagnostics record (DG_QP_ACT): the next solve may start warm
+    int pair_swap_bit;    // BatchIO::pair_swap_bit of the launch (-1 unless the two-wave kernel runs)
+    const char *err;
+};
+
+inline int format_name(const Row &r, char *buf, size_t len) { return snprintf(buf, len, "%s<%s>", r.base, r.tail); }
+
+// the rows of one kind a request may use: those of the first table that holds any (built in before a pack of the model's own tree
+// before a generic pack: the caller lists the tables in that order), and of these the ones built for the model's tree if there are such
+struct Candidates {
+    const Request &q;
+    int kind;
+    const Table *tab = nullptr;
+    bool specific = false;
+    bool usable(const Row &r) const {
+        return r.n == q.n && r.nb == q.nb && r.arith == q.arith && r.kind == kind && (r.nlv == 0 || r.nlv == q.levels) &&
+               (r.topo == 0 || (r.topo == 2 ? q.tree_match : r.topo == q.topo));
+    }
+    Candidates(const Request &q_, int kind_, const Table *tabs, int n_tabs) : q(q_), kind(kind_) {
+        for (int t = 0; t < n_tabs && !tab; t++)
+            for (int i = 0; i < tabs[t].count; i++)
+                if (usable(tabs[t].rows[i])) {
+                    tab = &tabs[t];
+                    specific = specific || tabs[t].rows[i].topo != 0;
+                }
+    }
+    const Row *pick(unsigned mask, unsigned want) const {  // the row whose flavour bits under `mask` are `want`
+        for (int i = 0; tab && i < tab->count; i++) {
+            const Row &r = tab->rows[i];
+            if (usable(r) && (r.topo != 0) == specific && (r.flavour & mask) == want) return &r;
+        }
+        return nullptr;
+    }
+};
+
+inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
+    Plan p{nullptr, 0, 0, false, -1, nullptr};
+    auto refuse = [&](const char *why) {
+        p.err = why;
+        return p;
+    };
+    auto run = [&](const Row *r, bool ws_valid_after) {
+        p.row = r;
+        p.threads = r->threads;
+        p.lds = r->lds;
+        p.ws_valid_after = ws_valid_after;
+        return p;
+    };
+    // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the
+    // synthetic COM link; QPs start cold and keep no working sets)
+    if (q.max_active > 2 || q.wide_tasks) {
+        if (q.reduced) return refuse("three active contacts / task levels of more than 6 dof: not built on the reduced dynamics path");
+        if (q.arith == kFloat) return refuse("three active contacts / task levels of more than 6 dof: fp64 batches only");
+        const Candidates gc(q, kGc, tabs, n_tabs);
+        const Row *r = gc.pick(kWideTasks, 0);
+        if (!r) return refuse("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
+        if (q.wide_tasks && !(r = gc.pick(kWideTasks, kWideTasks))) return refuse("task levels of more than 6 dof: built in for TOCABI's size only");
+        if (!q.hqp) return refuse("three active contacts / task levels of more than 6 dof: hqp = true only (the reference's closed-form redistribution is written for two contacts, src/dwbc.cpp:1570-1619)");
+        if (q.n_traj > 0 || q.n_custom > 0 || q.dump_on)
+            return refuse("three active contacts / task levels of more than 6 dof: link and COM tasks with f* from SetTaskSpace only (no trajectories, no TASK_CUSTOM levels, no dump record)");
+        return run(r, false);
+    }
+    const Candidates c(q, q.reduced ? kReduced : kCycle, tabs, n_tabs);
+    if (!c.tab) return refuse(q.arith == kFloat ? "no fp32 kernel for this model / number of task levels" : "no kernel for this model / number of task levels");
+    if (q.arith == kFloat && q.dump_on) return refuse("the dump record is not available on DWBC_F32 batches");
+    // the lean build (EXTRAS = false) serves every launch that uses none of the optional paths
+    const bool lean_asked = q.hqp && !q.warm && q.n_traj == 0 && !q.has_com_task && q.n_custom == 0 && !q.dump_on && !q.no_lean;
+    const bool lean = lean_asked && c.pick(kLean, kLean);
+    const bool wide = q.B <= 4 * q.n_cu && !q.no_wide && c.pick(kWide, kWide);
+    // the extras build of the full cycle leaves the working sets behind.  (fp32 batches go by the request alone, as they always have:
+    // a tree without a lean build starts warm one solve later.)
+    const bool ws_valid_after = q.arith == kFloat ? !lean_asked : (!lean && !q.reduced);
+    // two waves per instance, side chains on the helper wave: the lean fp64 cycle of small batches (one instance per SIMD)
+    if ((wide || q.pair_always) && lean && !q.reduced && q.arith == kDouble && !q.no_pair)
+        if (const Row *r = c.pick(kTwoWave, kTwoWave)) {
+            p.pair_swap_bit = q.pair_swap_bit;
+            return run(r, ws_valid_after);
+        }
+    const Row *r = c.pick(kWide | kLean | kTwoWave, (wide ? kWide : 0u) | (lean ? kLean : 0u));
+    return r ? run(r, ws_valid_after) : refuse("no kernel for this model / number of task levels");
+}
+
+}  // namespace dwbc_plan

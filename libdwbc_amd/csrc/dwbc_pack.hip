@@ -25,16 +25,21 @@ static_assert(DWBC_PACK_NB <= kMaxBodies, "body table");
 #define DWBC_PACK_TOPO TopoGeneric
 #define DWBC_PACK_KIND 0
 #endif
-#define DWBC_PACK_ENTRY(NLV)                                                                                                        \
-    {DWBC_PACK_N, DWBC_PACK_NB, NLV, DWBC_PACK_KIND, dwbc_cycle_kernel_v2<DWBC_PACK_N, DWBC_PACK_NB, NLV, kNT, true, DWBC_PACK_TOPO>,  \
-     Lds2<DWBC_PACK_N, DWBC_PACK_NB, NLV>::total_bytes, dwbc_cycle_kernel_v2w<DWBC_PACK_N, DWBC_PACK_NB, NLV, kNT, true, DWBC_PACK_TOPO>, \
-     dwbc_cycle_kernel_v2<DWBC_PACK_N, DWBC_PACK_NB, NLV, kNT, false, DWBC_PACK_TOPO>,                                               \
-     dwbc_cycle_kernel_v2w<DWBC_PACK_N, DWBC_PACK_NB, NLV, kNT, false, DWBC_PACK_TOPO>}
+#define DWBC_PACK_ROWS(NLV)                                                                  \
+    DWBC_ROWS_V2(DWBC_PACK_N, DWBC_PACK_NB, NLV, DWBC_PACK_TOPO, DWBC_PACK_KIND) \
+    DWBC_ROW_LEAN(DWBC_PACK_N, DWBC_PACK_NB, NLV, DWBC_PACK_TOPO, DWBC_PACK_KIND)
+static const dwbc_plan::Row kPack[] = {
 #ifdef DWBC_PACK_ONLY_NLV  // development: one level count only (a quarter of the compile time)
-static const KernelEntry kPack[] = {DWBC_PACK_ENTRY(DWBC_PACK_ONLY_NLV)};
+    DWBC_PACK_ROWS(DWBC_PACK_ONLY_NLV)
 #else
-static const KernelEntry kPack[] = {DWBC_PACK_ENTRY(1), DWBC_PACK_ENTRY(2), DWBC_PACK_ENTRY(3), DWBC_PACK_ENTRY(4)};
+    DWBC_PACK_ROWS(1) DWBC_PACK_ROWS(2) DWBC_PACK_ROWS(3) DWBC_PACK_ROWS(4)
 #endif
+// the general-contact kernel (dwbc_cycle_gc.h: up to three simultaneously active contacts) of this model size, when its QP rows fit one
+// per lane ((N - 6) torque rows + 30 cone rows <= 64)
+#if (DWBC_PACK_N - 6 + 10 * 3) <= 64
+    DWBC_ROW_GC(DWBC_PACK_N, DWBC_PACK_NB, 6, 0u)
+#endif
+};
 
 #ifdef DWBC_PACK_PARENTS
 // the tree this pack was compiled for: the loader compares it with the model's
@@ -43,15 +48,7 @@ extern "C" const int *dwbc_pack_parents(int *nb) {
     return TopoPack::parent;
 }
 #endif
-// the general-contact kernel (dwbc_cycle_gc.h: up to three simultaneously active contacts) of this model size, when its QP rows fit one
-// per lane ((N - 6) torque rows + 30 cone rows <= 64)
-#if (DWBC_PACK_N - 6 + 10 * 3) <= 64
-extern "C" const void *dwbc_pack_gc(int *lds_bytes) {
-    *lds_bytes = LdsG<DWBC_PACK_N, DWBC_PACK_NB, kGcContacts>::total_bytes;
-    return reinterpret_cast<const void *>(dwbc_cycle_kernel_gc<DWBC_PACK_N, DWBC_PACK_NB, kNT>);
-}
-#endif
-extern "C" const KernelEntry *dwbc_pack_table(int *count, unsigned *abi_tag) {
+extern "C" const dwbc_plan::Row *dwbc_pack_table(int *count, unsigned *abi_tag) {
     *count = (int)(sizeof(kPack) / sizeof(kPack[0]));
     *abi_tag = kernel_abi_tag();
     return kPack;

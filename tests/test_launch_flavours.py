@@ -1,7 +1,8 @@
 """-m gpu: every launch flavour of the full-model cycle kernel against the oracle.
 
-dwbc_batch_solve picks one of several builds of the same cycle (dwbc_capi.hip launch(), the table kKernels of dwbc_kernels.h):
-each has its own register budget and some their own LDS map, so lane ownership, LDS races and register-capped code generation can
+dwbc_batch_solve picks one of several builds of the same cycle (the planner of dwbc_launch_plan.h over the rows dwbc_kernels.h emits;
+tests/test_launch_plan.py checks the decision itself without a device):
+each build has its own register budget and some their own LDS map, so lane ownership, LDS races and register-capped code generation can
 differ between builds that share every line of arithmetic -- the host emulation (tests/emu) cannot see those.  The launcher's own
 switches force each route at a batch the oracle finishes in well under a second:
 
@@ -226,3 +227,53 @@ def test_natural_boundary_hqp_false():
     assert np.abs(tau[:, 2]).max() > 1.0
     assert (res[128][2] == st).all()
     assert np.abs(res[128][1] - tau).max() < XTOL
+
+
+LDS4_2LEVEL = 39152  # Lds4<39, 34, 2>::total_bytes (dwbc_cycle2p.h): dynamic LDS of the two-wave kernel for two task levels
+
+
+def test_pair_always_is_reported_as_launched(monkeypatch):
+    """DWBC_PAIR_ALWAYS=1 beyond 4 CU: the two-wave kernel runs and kernel_name() / launch_info() say so (they are the plan of the
+    launch); the answer is the compact build's on the same flat-footed states."""
+    nb = 4 * _n_cu() + 1
+    tasks, q, flags, fstar = cases.hierarchy_batch(nb, 2, seed=20261019)
+    res = {}
+    for env in ({}, {"DWBC_PAIR_ALWAYS": "1"}):
+        _set_env(monkeypatch, env)
+        wbc = _make(nb, tasks)
+        wbc.set_state(q)
+        wbc.set_contact(flags)
+        wbc.set_fstar_all(fstar)
+        wbc.solve()
+        res[len(env)] = wbc.kernel_name(), wbc.launch_info(), wbc.get("tau"), wbc.get("status")
+    assert res[0][0] == ROUTES["compact_lean"][1].format(L=2) and res[0][1][0] == 64, res[0][:2]
+    assert res[1][0] == ROUTES["two_wave"][1].format(L=2), res[1][0]
+    assert tuple(res[1][1]) == (128, LDS4_2LEVEL), res[1][1]
+    ok = res[0][3] == 1
+    assert (res[1][3] == res[0][3]).all() and ok.mean() > 0.9
+    assert np.abs(res[1][2][ok] - res[0][2][ok]).max() < XTOL
+
+
+def test_fp32_report_does_not_depend_on_a_solve(monkeypatch):
+    """kernel_name() / launch_info() of an fp32 batch before its first solve are those of the launch that follows"""
+    import libdwbc_amd as D
+
+    _set_env(monkeypatch, {})
+    nb = 64
+    tasks, q, flags, fstar = cases.hierarchy_batch(nb, 2, seed=20261020)
+    wbc = D.Batch(D.Model.from_urdf(cases.URDF), nb, device=0, dtype="f32")
+    for c in cases.CONTACTS_2:
+        wbc.add_contact(c["link"], c["point"], c["lx"], c["ly"], c["mu"], c["muz"])
+    for lv, links in enumerate(tasks):
+        for mode, link, pt in links:
+            wbc.add_task(lv, mode, link, pt)
+    wbc.set_torque_limit(np.array(cases.TAU_LIM))
+    wbc.set_state(q)
+    wbc.set_contact(flags)
+    wbc.set_fstar_all(fstar)
+    before = wbc.kernel_name(), tuple(wbc.launch_info())
+    wbc.solve()
+    assert wbc.get("status").mean() > 0.9
+    after = wbc.kernel_name(), tuple(wbc.launch_info())
+    assert before == after, (before, after)
+    assert after[0].startswith("dwbc_f32::") and after[1][0] == 64 and after[1][1] > 0, after
