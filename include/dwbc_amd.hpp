@@ -433,6 +433,39 @@ class RobotData {
         redistributed_ = true;
         return diag_[2];
     }
+    // CalcContactRedistribute(torque_input, hqp, init) (dwbc.h:297, src/dwbc.cpp:1377-1568): the redistribution of a torque that came
+    // from anywhere.  Its own lean kernel (dwbc_batch_redistribute), not the cycle: the state, contact flags and torque limit of the
+    // object are read, nothing the cycle computed is needed or changed.  On success cf_redis_qp_ is the QP's answer and
+    // torque_contact_ += NwJw * cf_redis_qp_; on failure torque_contact_ is zeroed.  As in the reference's sequence, the result lives in
+    // torque_contact_ only: a later CalcTaskControlTorque() / no-argument CalcContactRedistribute() on the same state writes the cycle's
+    // own torque_contact_ over it.
+    template <class V, class = decltype(std::declval<const V &>().data()), class = decltype(std::declval<const V &>().rows())>
+    int CalcContactRedistribute(const V &torque_input, bool hqp = true, bool init = true) { return CalcContactRedistribute(dwbc_amd::as_vec(torque_input), hqp, init); }
+    int CalcContactRedistribute(const Vec &torque_input, bool hqp = true, bool init = true) {
+        const bool size_ok = torque_input.size() == model_dof_;
+        if (init && !size_ok) std::cout << "Contact Redistribution : torque input size is not matched with model size" << std::endl;
+        if (!batch_ || !contact_ok_) return 0;
+        if (general_) { std::cout << "libdwbc_amd : CalcContactRedistribute(torque_input) is not served once the object runs the general-contact kernel (a third contact or a task level of more than 6 dof)" << std::endl; return 0; }
+        if (!hqp) { std::cout << "libdwbc_amd : CalcContactRedistribute(torque_input, hqp = false): the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque" << std::endl; return 0; }
+        if (!size_ok) { torque_contact_.assign(model_dof_, 0.0); return 0; }
+        if (!dwbc_batch_set_torque_input(batch_, torque_input.data()) || !dwbc_batch_redistribute(batch_, DWBC_SOLVE_HQP | (init ? DWBC_SOLVE_INIT : 0))) {
+            std::cout << "libdwbc_amd : " << dwbc_last_error() << std::endl;
+            return 0;
+        }
+        int st = 0;
+        double cf[6] = {0, 0, 0, 0, 0, 0};
+        Vec dt(model_dof_, 0.0);
+        dwbc_batch_get(batch_, DWBC_REDIST_STATUS, &st, sizeof(int));
+        dwbc_batch_get(batch_, DWBC_REDIST_CF, cf, sizeof cf);
+        dwbc_batch_get(batch_, DWBC_REDIST_TAU, dt.data(), dt.size() * 8);
+        const int k = contact_dof_ > 6 ? (int)contact_dof_ - 6 : 0;
+        if (k == 0) { torque_contact_.assign(model_dof_, 0.0); return st; }  // single support: nothing to redistribute (dwbc.cpp:1562-1567)
+        if (!st) { std::cout << "Contact QP solve failed" << std::endl; torque_contact_.assign(model_dof_, 0.0); return 0; }
+        cf_redis_qp_.assign(cf, cf + (k < 6 ? k : 6));
+        torque_contact_.resize(model_dof_, 0.0);
+        for (unsigned i = 0; i < model_dof_; i++) torque_contact_[i] += dt[i];
+        return 1;
+    }
     // ---- reduced (centroidal) dynamics model: the Reduced* call sequence (dwbc.h:411-416,
     //      tests/sp_test/redu_dyn_test.cpp:263-298).  One fused launch serves the whole sequence, like the full model.
     void ReducedDynamicsCalculate(bool = false) { if (!reduced_) dirty_ = true; reduced_ = true; }

@@ -54,11 +54,17 @@ enum dwbc_field {
     DWBC_IN_Q = 0,        /* (ndof+1)        f64  -- UpdateKinematics(q, ...)          */
     DWBC_IN_CONTACT = 1,  /* (n_contacts)    u8   -- SetContact(...)                   */
     DWBC_IN_FSTAR = 2,    /* (sum task dof)  f64  -- SetTaskSpace(level, f*) concatenated */
+    DWBC_IN_TORQUE = 3,   /* (m)             f64  -- torque_input of CalcContactRedistribute(torque_input, ...) (dwbc_batch_redistribute) */
     /* outputs (bindable) */
     DWBC_TAU = 10,        /* (3, m) f64: torque_grav_, torque_task_, torque_contact_  (include/dwbc.h:115-117) */
     DWBC_WRENCH = 11,     /* (12; 18 after dwbc_batch_set_max_active_contacts(b, 3)) f64: getContactForce(tau_total), zero padded (src/dwbc.cpp:891-896) */
     DWBC_STATUS = 12,     /* (1)    i32: 1 ok / 0 failed                               */
     DWBC_DIAG = 13,       /* (90)   i32: stage status, QP iterations, working sets, stage stamps */
+    /* outputs of dwbc_batch_redistribute (bindable) */
+    DWBC_REDIST_TAU = 14,    /* (m)     f64: NwJw c, what CalcContactRedistribute(torque_input) adds to torque_contact_ (src/dwbc.cpp:1549) */
+    DWBC_REDIST_CF = 15,     /* (6)     f64: c = cf_redis_qp_, zero beyond the contact-null dimension */
+    DWBC_REDIST_WRENCH = 16, /* (2, 12) f64: getContactForce(torque_input), getContactForce(torque_input + NwJw c); zero padded */
+    DWBC_REDIST_STATUS = 17, /* (1)     i32: 1 ok / 0 failed */
     /* derived getters (host only) */
     DWBC_TAU_GRAV = 20, DWBC_TAU_TASK = 21, DWBC_TAU_CONTACT = 22, DWBC_TAU_TOTAL = 23,
     /* intermediates, available after a solve with dwbc_batch_enable_dump(b, 1) -- the RobotData public fields */
@@ -192,7 +198,7 @@ int dwbc_batch_set_fstar(dwbc_batch *b, int level, const double *fstar);
  * limit and control time of `src` into `dst` (same model and batch size); the hand-off the reference uses between threads */
 int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src);
 
-/* page-locked host mirror of an input field (DWBC_IN_Q, DWBC_IN_CONTACT, DWBC_IN_FSTAR; NULL for anything else or before the
+/* page-locked host mirror of an input field (DWBC_IN_Q, DWBC_IN_CONTACT, DWBC_IN_FSTAR, DWBC_IN_TORQUE; NULL for anything else or before the
  * field has a size): a caller that assembles its states directly in this memory and passes the same pointer to
  * dwbc_batch_set_state / set_contact (or calls dwbc_batch_set_fstar with pointers into it -- level l starts at column
  * fstar offset of l) skips the host-side copy; the upload is one asynchronous PCIe transfer on the batch's stream.
@@ -218,6 +224,26 @@ size_t dwbc_batch_field_bytes(const dwbc_batch *b, int field);
 int dwbc_batch_launch_info(const dwbc_batch *b, int *threads_per_instance, int *lds_bytes);
 /* name of the kernel the next dwbc_batch_solve will launch (as rocprofv3 prints it), for bench / profile bookkeeping */
 const char *dwbc_batch_kernel_name(const dwbc_batch *b);
+
+/* ---- CalcContactRedistribute(torque_input, hqp, init) + getContactForce(torque) for a CALLER-SUPPLIED joint torque (reference
+ * include/dwbc.h:297,303, src/dwbc.cpp:1377-1568, src/wbd.cpp:268-271): a torque that came from anywhere -- a policy, a clipped command,
+ * another controller -- gets the contact-null-space torque NwJw c that brings the contact wrenches back inside the ZMP / friction rows
+ * and the torque limits (DWBC_REDIST_TAU, DWBC_REDIST_CF), and the contact wrench before and after it (DWBC_REDIST_WRENCH).  One lean
+ * kernel of its own (kinematics to NwJw and one QP of at most six variables; no task level, no gravity torque): it reads the state, the
+ * contact flags and the torque limit of the batch, needs no task space, and leaves DWBC_TAU, DWBC_WRENCH, DWBC_STATUS, DWBC_DIAG, the
+ * dump record and the warm-start state of dwbc_batch_solve untouched, so the two may be called on one batch in either order.
+ * Per instance: one active contact -> zero torque, status 1 (the wrenches are still evaluated); none -> zeros, status 1; more than two
+ * flags raised, a failed contact stage or a failed QP -> status 0, zero torque.
+ * Refused (dwbc_last_error): DWBC_F32 batches, dwbc_batch_set_max_active_contacts(b, 3), a model without the kernel (built in for
+ * TOCABI's size and tree), DWBC_SOLVE_HQP clear (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque), and a
+ * torque input that was never set.  DWBC_SOLVE_INIT clear is accepted and runs cold: the QP is strictly convex, its point does not
+ * depend on the start. */
+int dwbc_batch_set_torque_input(dwbc_batch *b, const double *tau);   /* B x m; the mirror of dwbc_batch_host_ptr(b, DWBC_IN_TORQUE) is taken in place */
+int dwbc_batch_redistribute(dwbc_batch *b, unsigned flags);          /* asynchronous on the batch's stream */
+/* K back-to-back redistributions bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float *ms);
+/* name of the kernel dwbc_batch_redistribute launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b);
 
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least

@@ -86,6 +86,11 @@ SYMBOLS = [
     ("dwbc_batch_solve_jacc_r_nc", _i, [_vp, _vp, _i, _i]),
     ("dwbc_batch_get_jacc_nc", _i, [_vp, _i, _vp, C.c_size_t]),
     ("dwbc_batch_host_ptr", _vp, [_vp, _i]),
+    # redistribution of a caller-supplied torque
+    ("dwbc_batch_set_torque_input", _i, [_vp, _vp]),
+    ("dwbc_batch_redistribute", _i, [_vp, C.c_uint]),
+    ("dwbc_batch_time_redistribute", _i, [_vp, C.c_uint, _i, C.POINTER(C.c_float)]),
+    ("dwbc_batch_redistribute_kernel_name", C.c_char_p, [_vp]),
 ]
 
 _lib = None

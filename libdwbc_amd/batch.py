@@ -8,6 +8,8 @@
     wbc.set_state(q); wbc.set_contact(flags); wbc.set_fstar(level, f)   # UpdateKinematics / SetContact / SetTaskSpace
     wbc.solve()                                        # CalcContactConstraint .. CalcContactRedistribute, one launch
     tau = wbc.get("tau_total")
+    wbc.set_torque_input(tau_policy); wbc.redistribute()   # CalcContactRedistribute(torque_input): any torque, its own lean kernel
+    tau_policy + wbc.get("redist_tau")
 
 All arithmetic happens in libdwbc_hip.so (hand-written HIP, gfx950).  torch is only used, optionally, to own
 device buffers and streams (bind_tensor) and for torch.distributed in bench.py.
@@ -26,7 +28,8 @@ SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
 
 # field ids of include/dwbc_batch.h
 FIELDS = dict(
-    in_q=0, in_contact=1, in_fstar=2, tau=10, wrench=11, status=12, diag=13,
+    in_q=0, in_contact=1, in_fstar=2, in_torque=3, tau=10, wrench=11, status=12, diag=13,
+    redist_tau=14, redist_cf=15, redist_wrench=16, redist_status=17,
     tau_grav=20, tau_task=21, tau_contact=22, tau_total=23,
     A=30, A_inv=31, J_C=32, Lambda_c=33, J_C_INV_T=34, A_inv_N_C=35, W_inv=36, NwJw=37, G=38, P_C=39,
     link_R=40, link_p=41, fstar_qp=42, contact_qp=43, cf_redis=44, J_task=45, Lambda_task=46, J_kt=47, qp_viol=48,
@@ -288,8 +291,9 @@ class Batch:
             lv += 1
 
     def host_view(self, field):
-        """numpy view of the page-locked host mirror of an input field ("in_q", "in_contact", "in_fstar"): fill it in place and pass
-        it to set_state / set_contact / set_fstar_all -- the host-side copy is skipped, the upload is one asynchronous transfer"""
+        """numpy view of the page-locked host mirror of an input field ("in_q", "in_contact", "in_fstar", "in_torque"): fill it in place and
+        pass it to set_state / set_contact / set_fstar_all / set_torque_input -- the host-side copy is skipped, the upload is one
+        asynchronous transfer"""
         shape = (self.B,) + tuple(self._SHAPES[field](self))
         dt = np.uint8 if field == "in_contact" else np.float64
         p = self._L.dwbc_batch_host_ptr(self._h, FIELDS[field])
@@ -321,6 +325,32 @@ class Batch:
     def sync(self):
         _check(self._L.dwbc_batch_sync(self._h))
 
+    # ---- CalcContactRedistribute(torque_input, hqp, init) + getContactForce(torque) for a caller-supplied torque
+    def set_torque_input(self, tau):
+        """torque_input (B, m) of the next redistribute(); a tensor bound as "in_torque" is read in place instead"""
+        t = np.ascontiguousarray(tau, np.float64)
+        assert t.shape == (self.B, self.m), t.shape
+        _check(self._L.dwbc_batch_set_torque_input(self._h, t.ctypes.data))
+
+    def redistribute(self, hqp=True, init=True):
+        """The contact-null-space torque NwJw c that brings the contact wrenches of the supplied torque back inside the ZMP / friction
+        rows and the torque limits (reference include/dwbc.h:297, src/dwbc.cpp:1377-1568): get("redist_tau") (B, m), the QP's answer
+        get("redist_cf") (B, 6), the wrench before and after the correction get("redist_wrench") (B, 2, 12), get("redist_status").
+        One lean kernel on the batch's stream, asynchronous; reads the state, contact flags and torque limit of the batch and leaves
+        every output of solve() alone.  init=False is accepted and runs cold; hqp=False is refused."""
+        _check(self._L.dwbc_batch_redistribute(self._h, (SOLVE_HQP if hqp else 0) | (SOLVE_INIT if init else 0)))
+
+    def time_redistributes(self, steps):
+        ms = C.c_float(0)
+        _check(self._L.dwbc_batch_time_redistribute(self._h, SOLVE_HQP | SOLVE_INIT, int(steps), C.byref(ms)))
+        return ms.value
+
+    def redistribute_kernel_name(self):
+        name = self._L.dwbc_batch_redistribute_kernel_name(self._h).decode()
+        if not name:
+            raise DwbcError(_lib.last_error())
+        return name
+
     def time_solves(self, steps, reduced=False):
         ms = C.c_float(0)
         _check(self._L.dwbc_batch_time_solves(self._h, SOLVE_HQP | SOLVE_INIT | (SOLVE_REDUCED if reduced else 0), int(steps), C.byref(ms)))
@@ -346,13 +376,14 @@ class Batch:
         B=lambda s: (s.n,), link_v=lambda s: (48, 3), link_w=lambda s: (48, 3),
         contact_pos=lambda s: (2, 3), contact_rot=lambda s: (2, 3, 3), zmp=lambda s: (3, 3),
         A_R=lambda s: (24, 24), A_R_inv=lambda s: (24, 24), G_R=lambda s: (24,), J_I_nc=lambda s: (6, s.n - 12), J_I_nc_inv_T=lambda s: (6, s.n - 12),
-        in_q=lambda s: (s.n + 1,), in_contact=lambda s: (s.n_contacts,), in_fstar=lambda s: (s.fstar_size,),
+        in_q=lambda s: (s.n + 1,), in_contact=lambda s: (s.n_contacts,), in_fstar=lambda s: (s.fstar_size,), in_torque=lambda s: (s.m,),
+        redist_tau=lambda s: (s.m,), redist_cf=lambda s: (6,), redist_wrench=lambda s: (2, 12), redist_status=lambda s: (),
     )
 
     def get(self, field):
         fid = FIELDS[field]
         shape = (self.B,) + tuple(self._SHAPES[field](self))
-        dt = np.int32 if field in ("status", "diag") else (np.uint8 if field == "in_contact" else np.float64)
+        dt = np.int32 if field in ("status", "diag", "redist_status") else (np.uint8 if field == "in_contact" else np.float64)
         out = np.zeros(shape, dtype=dt)
         nbytes = self._L.dwbc_batch_field_bytes(self._h, fid)
         assert nbytes == out.nbytes, (field, nbytes, out.nbytes)

@@ -305,6 +305,7 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     hipMemset(b->d_diag, 0, (size_t)B * DG_COUNT * sizeof(int));
     hipMemset(b->d_status, 0, (size_t)B * sizeof(int));
     b->h_q.assign((size_t)B * (b->n + 1), 0.0);
+    b->h_tau_in.assign((size_t)B * b->m, 0.0);
     return b;
 }
 
@@ -322,6 +323,11 @@ void dwbc_batch_destroy(dwbc_batch *b) {
     if (b->own_tau) hipFree(b->d_tau);
     if (b->own_wrench) hipFree(b->d_wrench);
     if (b->own_status) hipFree(b->d_status);
+    if (b->own_tau_in) hipFree(b->d_tau_in);
+    if (b->own_rd_tau) hipFree(b->d_rd_tau);
+    if (b->own_rd_cf) hipFree(b->d_rd_cf);
+    if (b->own_rd_wrench) hipFree(b->d_rd_wrench);
+    if (b->own_rd_status) hipFree(b->d_rd_status);
     hipFree(b->d_diag);
     hipFree(b->d_total);
     for (int l = 0; l < kMaxLevels; l++) hipFree(b->d_jacc[l]);
@@ -547,6 +553,7 @@ void *dwbc_batch_host_ptr(dwbc_batch *b, int field) {
         case DWBC_IN_Q: return b->h_q.empty() ? nullptr : b->h_q.data();
         case DWBC_IN_CONTACT: return b->h_flags.empty() ? nullptr : b->h_flags.data();
         case DWBC_IN_FSTAR: return b->h_fstar.empty() ? nullptr : b->h_fstar.data();
+        case DWBC_IN_TORQUE: return b->h_tau_in.empty() ? nullptr : b->h_tau_in.data();
         default: return nullptr;
     }
 }
@@ -561,6 +568,11 @@ int dwbc_batch_bind_device(dwbc_batch *b, int field, void *p) {
         case DWBC_TAU: if (b->own_tau) hipFree(b->d_tau); b->d_tau = (double *)p; b->own_tau = false; return 1;
         case DWBC_WRENCH: if (b->own_wrench) hipFree(b->d_wrench); b->d_wrench = (double *)p; b->own_wrench = false; return 1;
         case DWBC_STATUS: if (b->own_status) hipFree(b->d_status); b->d_status = (int *)p; b->own_status = false; return 1;
+        case DWBC_IN_TORQUE: if (b->own_tau_in) hipFree(b->d_tau_in); b->d_tau_in = (double *)p; b->own_tau_in = false; b->dirty_tau_in = false; b->tau_in_set = true; return 1;
+        case DWBC_REDIST_TAU: if (b->own_rd_tau) hipFree(b->d_rd_tau); b->d_rd_tau = (double *)p; b->own_rd_tau = false; return 1;
+        case DWBC_REDIST_CF: if (b->own_rd_cf) hipFree(b->d_rd_cf); b->d_rd_cf = (double *)p; b->own_rd_cf = false; return 1;
+        case DWBC_REDIST_WRENCH: if (b->own_rd_wrench) hipFree(b->d_rd_wrench); b->d_rd_wrench = (double *)p; b->own_rd_wrench = false; return 1;
+        case DWBC_REDIST_STATUS: if (b->own_rd_status) hipFree(b->d_rd_status); b->d_rd_status = (int *)p; b->own_rd_status = false; return 1;
         default: return fail("field cannot be bound");
     }
 }
@@ -686,6 +698,107 @@ int dwbc_batch_solve(dwbc_batch *b, unsigned flags) {
     return launch(b, reduced);
 }
 
+// ---- CalcContactRedistribute(torque_input, hqp, init) on a caller-supplied torque: the lean kernel of dwbc_redistribute.h
+int dwbc_batch_set_torque_input(dwbc_batch *b, const double *tau) {
+    if (!tau) return fail("torque input is NULL");
+    if (b->d_tau_in && !b->own_tau_in) return fail("the torque input is bound to a device buffer");
+    wait_uploads(b);
+    if (tau != b->h_tau_in.data()) memcpy(b->h_tau_in.data(), tau, b->h_tau_in.size() * sizeof(double));  // (dwbc_batch_host_ptr: already in place)
+    b->dirty_tau_in = true;
+    b->tau_in_set = true;
+    return 1;
+}
+
+// the planner's view of a redistribution on this batch: the model, the arithmetic type and the contact capacity of the batch, hqp of
+// the call (the cycle's own hqp / warm state is neither read nor changed)
+static dwbc_plan::Plan redist_plan(const dwbc_batch *b, bool hqp) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.redistribute = true;
+    q.hqp = hqp;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+
+static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    const void *fn = p.row->fn;
+    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        b->lds_attr_set.push_back(fn);
+    }
+    BatchIO io{};  // what stage 0 and the contact stage read; no output of the cycle is named
+    io.B = b->B;
+    io.q = b->d_q;
+    io.flags = b->d_flags;
+    io.fstar = b->d_fstar;
+    io.body = b->d_body;
+    io.topo = b->d_topo;
+    io.hqp = 1;
+    io.pair_swap_bit = -1;
+    RedistIO rio{b->d_tau_in, b->d_rd_tau, b->d_rd_cf, b->d_rd_wrench, b->d_rd_status};
+    void *args[] = {(void *)&b->su, (void *)&io, (void *)&rio};
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    return 1;
+}
+
+// uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+static int redistribute_once(dwbc_batch *b, unsigned flags, dwbc_plan::Plan *planned) {
+    // (DWBC_SOLVE_INIT clear is accepted: the one QP is strictly convex and starts cold either way)
+    const dwbc_plan::Plan p = redist_plan(b, (flags & DWBC_SOLVE_HQP) != 0);
+    if (!p.row) return fail(p.err);
+    if (flags & DWBC_SOLVE_REDUCED) return fail("redistribution of a supplied torque: not built on the reduced dynamics path");
+    if (b->su.n_contacts < 1) return fail("no contact constraint");
+    if (!b->tau_in_set) return fail("no torque input: call dwbc_batch_set_torque_input (or bind DWBC_IN_TORQUE) first");
+    HIP_OK(hipSetDevice(b->device));
+    if (!upload_inputs(b)) return 0;
+    const size_t B = b->B, m = b->m;
+    if (!b->d_tau_in) { HIP_OK(hipMalloc(&b->d_tau_in, B * m * sizeof(double))); b->own_tau_in = true; b->dirty_tau_in = true; }
+    if (b->dirty_tau_in && b->own_tau_in) {
+        HIP_OK(hipMemcpyAsync(b->d_tau_in, b->h_tau_in.data(), b->h_tau_in.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (!b->ev_upload) HIP_OK(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
+        HIP_OK(hipEventRecord(b->ev_upload, b->stream));
+        b->upload_pending = true;
+    }
+    b->dirty_tau_in = false;
+    if (!b->d_rd_tau) { HIP_OK(hipMalloc(&b->d_rd_tau, B * m * sizeof(double))); b->own_rd_tau = true; }
+    if (!b->d_rd_cf) { HIP_OK(hipMalloc(&b->d_rd_cf, B * 6 * sizeof(double))); b->own_rd_cf = true; }
+    if (!b->d_rd_wrench) { HIP_OK(hipMalloc(&b->d_rd_wrench, B * 24 * sizeof(double))); b->own_rd_wrench = true; }
+    if (!b->d_rd_status) { HIP_OK(hipMalloc(&b->d_rd_status, B * sizeof(int))); b->own_rd_status = true; }
+    if (planned) *planned = p;
+    return launch_redistribute(b, p);
+}
+
+int dwbc_batch_redistribute(dwbc_batch *b, unsigned flags) { return redistribute_once(b, flags, nullptr); }
+
+int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float *ms) {
+    HIP_OK(hipSetDevice(b->device));
+    dwbc_plan::Plan p{};
+    if (!redistribute_once(b, flags, &p)) return 0;  // uploads + warm launch
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    // the events are destroyed on every way out (a failed step has set the error string)
+    auto timed = [&]() -> int {
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, b->stream));
+        for (int i = 0; i < steps; i++)
+            if (!launch_redistribute(b, p)) return 0;
+        HIP_OK(hipEventRecord(e1, b->stream));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(ms, e0, e1));
+        return 1;
+    };
+    const int ok = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+
+const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = redist_plan(b, true);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
+
 int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     // RobotData::CopyKinematicsData (reference src/dwbc.cpp:1711-1762): state, contacts (with their flags), task spaces (with
     // their f*), torque limit and control time go to the target object, which then runs its own Calc* sequence.  Everything
@@ -773,6 +886,10 @@ size_t dwbc_batch_field_bytes(const dwbc_batch *b, int field) {
         case DWBC_WRENCH: return B * 6 * b->max_active * 8;
         case DWBC_STATUS: return B * 4;
         case DWBC_DIAG: return B * DG_COUNT * 4;
+        case DWBC_IN_TORQUE: case DWBC_REDIST_TAU: return B * m * 8;
+        case DWBC_REDIST_CF: return B * 6 * 8;
+        case DWBC_REDIST_WRENCH: return B * 24 * 8;
+        case DWBC_REDIST_STATUS: return B * 4;
         case DWBC_TAU_GRAV: case DWBC_TAU_TASK: case DWBC_TAU_CONTACT: case DWBC_TAU_TOTAL: return B * m * 8;
         case DWBC_A: case DWBC_A_INV: case DWBC_A_INV_N_C: return B * n * n * 8;
         case DWBC_J_C: case DWBC_J_C_INV_T: return B * 12 * n * 8;
@@ -828,6 +945,12 @@ int dwbc_batch_get(dwbc_batch *b, int field, void *out, size_t bytes) {
         case DWBC_WRENCH: return d2h(b->d_wrench, need);
         case DWBC_STATUS: return d2h(b->d_status, need);
         case DWBC_DIAG: return d2h(b->d_diag, need);
+        case DWBC_IN_TORQUE: return b->d_tau_in ? d2h(b->d_tau_in, need) : fail("no torque input on the device yet");
+        case DWBC_REDIST_TAU: case DWBC_REDIST_CF: case DWBC_REDIST_WRENCH: case DWBC_REDIST_STATUS: {
+            const void *src = field == DWBC_REDIST_TAU ? (const void *)b->d_rd_tau : field == DWBC_REDIST_CF ? (const void *)b->d_rd_cf
+                              : field == DWBC_REDIST_WRENCH ? (const void *)b->d_rd_wrench : (const void *)b->d_rd_status;
+            return src ? d2h(src, need) : fail("no redistribution output yet: call dwbc_batch_redistribute first");
+        }
         case DWBC_TAU_GRAV: case DWBC_TAU_TASK: case DWBC_TAU_CONTACT: case DWBC_TAU_TOTAL: {
             // one third of the bytes over PCIe: the part (or the sum, getTorqueCommand-style) is formed on the device
             if (!b->d_total) HIP_OK(hipMalloc(&b->d_total, B * m * sizeof(double)));

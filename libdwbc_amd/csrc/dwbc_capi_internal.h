@@ -103,6 +103,12 @@ struct dwbc_batch {
     hipEvent_t ev_upload = nullptr;
     bool upload_pending = false;
     int n_cu = 0;  // compute units of the batch's device
+    // dwbc_batch_redistribute: torque input (B x m; the mirror is created with the batch) and the outputs, allocated at the first launch
+    double *d_tau_in = nullptr, *d_rd_tau = nullptr, *d_rd_cf = nullptr, *d_rd_wrench = nullptr;
+    int *d_rd_status = nullptr;
+    bool own_tau_in = false, own_rd_tau = false, own_rd_cf = false, own_rd_wrench = false, own_rd_status = false;
+    dwbc::PinnedVec<double> h_tau_in;
+    bool dirty_tau_in = false, tau_in_set = false;
     dwbc::DumpLayout dl{};
 };
 

@@ -10,6 +10,7 @@
 #include "dwbc_reduced.h"
 #include "dwbc_cycle2p.h"
 #include "dwbc_cycle_gc.h"
+#include "dwbc_redistribute.h"
 
 namespace dwbc {
 
@@ -84,6 +85,17 @@ __global__ __launch_bounds__(NT) void dwbc_cycle_kernel_reduced(const Setup su, 
     cycle_instance_reduced<N, NB, NLV, NT, Topo>(th, su, io, inst, lds, iL);
 }
 
+// contact redistribution of a caller-supplied torque (dwbc_redistribute.h): the front half of the cycle and one six-variable QP on the
+// compact map's footprint -- register-capped like `_v2`, eight workgroups per CU
+template <int N, int NB, class Topo>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_redistribute_kernel(const Setup su, const BatchIO io, const RedistIO rio) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    redistribute_instance<N, NB, 64, Topo>(th, su, io, rio, inst, lds);
+}
+
 #define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
@@ -127,6 +139,13 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_PAIR(NLV) \
     DWBC_ROW(39, 34, NLV, 1, kCycle, lp::kLean | lp::kTwoWave, (Lds4<39, 34, NLV>::total_bytes), 2 * kNT, dwbc_cycle_kernel_v2p, 39, 34, NLV, dwbc::TopoTocabi),
 #endif
+// the redistribution kernel: fp64, TOCABI's constant tree (DWBC_NO_REDIST_KERNEL: fp32); not part of a kernel pack
+#ifdef DWBC_NO_REDIST_KERNEL
+#define DWBC_ROW_REDIST(N, NB, TOPO, TK)
+#else
+#define DWBC_ROW_REDIST(N, NB, TOPO, TK) \
+    DWBC_ROW(N, NB, 0, TK, kRedist, 0u, (LdsRd<N, NB>::total_bytes), kNT, dwbc_redistribute_kernel, N, NB, dwbc::TOPO),
+#endif
 // instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
 // and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
 // model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
@@ -146,6 +165,7 @@ const lp::Row kRows[] = {
     DWBC_ROWS_TOCABI_ANY(1) DWBC_ROWS_TOCABI_ANY(2) DWBC_ROWS_TOCABI_ANY(3) DWBC_ROWS_TOCABI_ANY(4)
 #endif
     DWBC_ROW_GC(39, 34, 6, 0u) DWBC_ROW_GC(39, 34, 12, lp::kWideTasks)
+    DWBC_ROW_REDIST(39, 34, TopoTocabi, 1)
 };
 #endif
 

@@ -1,5 +1,5 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve: the table row of every launchable kernel and the one
-// function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque):
+// the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
 #pragma once
@@ -8,7 +8,8 @@
 namespace dwbc_plan {
 
 enum Arith { kDouble = 0, kFloat = 1 };
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2 };  // full-model cycle, reduced (centroidal) dynamics, general-contact cycle
+// full-model cycle, reduced (centroidal) dynamics, general-contact cycle, redistribution of a caller-supplied torque (dwbc_redistribute.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -51,6 +52,9 @@ struct Request {
     // DWBC_PAIR_SWAP_BIT (-1: unset)
     bool no_wide, no_pair, no_lean, pair_always;
     int pair_swap_bit;
+    // not a cycle: CalcContactRedistribute(torque_input, hqp, init) on a caller-supplied torque (dwbc_batch_redistribute); of the members
+    // above it reads the model, arith, max_active and hqp
+    bool redistribute = false;
 };
 
 struct Plan {
@@ -104,6 +108,16 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         p.ws_valid_after = ws_valid_after;
         return p;
     };
+    // redistribution of a caller-supplied torque: one lean kernel, whatever the batch size or the task set-up (it runs no task level and
+    // starts its one QP cold)
+    if (q.redistribute) {
+        if (q.arith == kFloat) return refuse("redistribution of a supplied torque: fp64 batches only");
+        if (q.max_active > 2) return refuse("redistribution of a supplied torque: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
+        const Row *r = Candidates(q, kRedist, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no redistribution kernel for this model (built in for TOCABI's size and tree; kernel packs do not carry one)");
+        if (!q.hqp) return refuse("redistribution of a supplied torque: hqp = true only (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque)");
+        return run(r, false);
+    }
     // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the
     // synthetic COM link; QPs start cold and keep no working sets)
     if (q.max_active > 2 || q.wide_tasks) {

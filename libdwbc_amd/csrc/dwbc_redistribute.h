@@ -1,0 +1,293 @@
+// dwbc_redistribute.h -- contact redistribution of a CALLER-SUPPLIED joint torque, one wavefront per instance:
+//   RobotData::CalcContactRedistribute(torque_input, hqp = true, init)   reference include/dwbc.h:297, src/dwbc.cpp:1377-1568
+//   RobotData::getContactForce(command_torque)                           reference include/dwbc.h:303, src/wbd.cpp:268-271
+// The torque comes from anywhere (a policy, a clipped command, another controller); the kernel returns the contact-null-space torque
+// NwJw c that brings the contact wrenches back inside the ZMP / friction rows and the torque limits, the QP's answer c, and the contact
+// wrench before and after the correction.  It is the front half of the fused cycle and one QP of k = cd - 6 variables:
+//   stage 0 (dwbc_cycle2_stage0.inc, shared text)   kinematics, CRBA, tree-sparse A^-1 sweep
+//   stage 1 (below)                                 contact frames, J_C, Y = J_C A^-1, Lambda_c, Jbar^T = Lambda_c Y, P_C = Jbar^T G
+//   NwJw                                            closed form from the internal-wrench basis (as dwbc_cycle2.h forms it)
+//   wrench maps                                     FN = Jbar[:, 6:] [tau_in | NwJw]  (cd x 7), rotated into the contact frames for the cone rows
+//   QP                                              min |c|^2  s.t.  +-NwJw c <= tau_lim -+ tau_in,  10 cone rows per active contact
+//                                                   (dwbc.cpp:1458-1517; qp_solve_wave, cold start at c = 0, accepted at kQpFeasTol)
+// What the cycle needs beyond that is never formed here: no A^-1 N_c (the register columns stay A^-1), no W, no W^+, no gravity torque,
+// no task block.
+#pragma once
+#include "dwbc_cycle2.h"
+
+namespace dwbc {
+
+// device pointers of a redistribution launch that BatchIO has no member for (BatchIO's layout is part of the kernel-pack ABI and stays)
+struct RedistIO {
+    const io_t *tau_in;  // B x M   torque_input
+    io_t *tau;           // B x M   NwJw c (what the reference adds to torque_contact_)
+    io_t *cf;            // B x 6   c (cf_redis_qp_), zero beyond k
+    io_t *wrench;        // B x 2 x 12: getContactForce(tau_in), getContactForce(tau_in + NwJw c); zero padded
+    int *status;         // B       1 ok / 0 failed
+};
+
+// LDS map: the compact map's stage-0 / stage-1 / NwJw placement (Lds3 at one task level, dwbc_cycle2.h) -- those stages are the same
+// text -- with the blocks behind them named for what this kernel keeps there.  Life times (region : stage 0 | stage 1 | NwJw | maps + QP):
+//   head : q, G ............. G (P_C) | .    | .
+//   JbT  : k_S k_F          | J_C, then Jbar^T .......................... (maps, wrench outputs)
+//   NwJw : .                | .              | NwJw .................... (QP rows, torque output)
+//   U    : Rw               | Rw (contact frames, pelvis rotation)  | . | .
+//   RE   : pw aw ........................... | .    | tau_in, rotated maps, fv, QP scratch
+//   RF   : k_Iw k_Ic (k_Rl, k_A over them) | Vb ........... | (QP scratch reaches into it)
+//   RG   : (k_Ic, k_A)      | Y              | .    | .
+//   RX   : (k_A), sweep column | Lambda_c, small-inverse scratch ... | FN (unrotated maps, kept for the wrench outputs)
+// The size is set by stage 0: the row-packed mass matrix (N (N + 1) / 2 doubles) staged beside S, F, the link frames and the state.
+// TOCABI: 20 432 B, eight workgroups per CU.
+template <int N, int NB>
+struct LdsRd : Lds3<N, NB, 1> {
+    using Base = Lds3<N, NB, 1>;
+    static constexpr int FLD = 8;                // row stride of FN: 1 + K columns, padded to an even number
+    static constexpr int t_in = Base::t_base;    // M: tau_in (the `base` of the QP's torque rows)
+    static constexpr int fn = Base::c_s2;        // C x FLD: Jbar[:, 6:] [tau_in | NwJw], world frame
+    static_assert(Base::C * FLD <= Base::C * Base::C, "FN borrows the input block of the small inverses");
+    static_assert(1 + Base::K <= FLD && 1 + Base::K <= Base::WLD, "columns of the wrench maps");
+};
+
+template <int N, int NB, int NT, class Topo>
+DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, const RedistIO &rio, int inst, real_t *L) {
+    using S = LdsRd<N, NB>;
+    constexpr bool kExtras = false;
+    constexpr int M = S::M, C = S::C, WLD = S::WLD, FLD = S::FLD;
+    DWBC_LANE_DECL;
+    constexpr bool kTree = !std::is_same<Topo, TopoGeneric>::value;
+    const int nb = kTree ? NB : su.nb;
+    const real_t *body = io.body;
+    const int *topo = io.topo;  // parent[nb] depth[nb] subtree[nb]
+    const io_t *qin = io.q + (size_t)inst * (N + 1);
+    const DumpLayout dl = DumpLayout::make(N);
+    real_t *dump = nullptr;  // no dump record, no diagnostics: the cycle's stay as its last launch left them
+    int *diag = nullptr;
+    DWBC_STAMP_INIT();
+
+    PLA(real_t, s, N);  // column `lane` of A -> A^-1
+    PL(real_t, dg);     // its diagonal element
+
+#include "dwbc_cycle2_stage0.inc"
+
+    // ================= stage 1: contacts (dwbc.h:432-474, dwbc.cpp:433-478, wbd.cpp:108-143), without A^-1 N_c =================
+    const unsigned char *fl = io.flags + (size_t)inst * su.n_contacts;
+    int act_c[kMaxActiveContacts] = {0, 0};
+    int nc = 0, nflag = 0;
+    for (int i = 0; i < su.n_contacts; i++) {
+        if (fl[i] && nc < kMaxActiveContacts) act_c[nc++] = i;
+        nflag += fl[i] ? 1 : 0;
+    }
+    const bool too_many = nflag > kMaxActiveContacts;  // as the cycle: never solved with a subset, the instance fails
+    if (too_many) st_contact = 0;
+    const int cd = 6 * nc, k = cd > 6 ? cd - 6 : 0;
+    DWBC_SYNC();
+    for (int a = 0; a < nc; a++) {
+        const int ci = act_c[a], link = su.c_link[ci];
+        const real_t *R = L + S::Rw + link * 9;
+        for (int r = th.tid; r < 12; r += NT) {
+            if (r < 9) L[S::Rc + a * 9 + r] = R[r];
+            else {
+                const int x = r - 9;
+                L[S::Pc + a * 3 + x] = L[S::pw + link * 3 + x] + R[x * 3] * su.c_point[ci][0] + R[x * 3 + 1] * su.c_point[ci][1] + R[x * 3 + 2] * su.c_point[ci][2];
+            }
+        }
+    }
+    for (int r = th.tid; r < 9; r += NT) L[S::Rw0 + r] = L[S::Rw + r];  // pelvis rotation for the base columns of the point Jacobians
+    DWBC_SYNC();
+    // J_C and Y = J_C A^-1 TRANSPOSED in LDS (N x C), as in the cycle; Jbar^T (C x N) is written over J_C once Y and Lambda_c are done
+    real_t *JCt = L + S::c_JC, *Yt = L + S::c_Y, *Lam = L + S::c_Lam, *JbT = L + S::JbT, *Vb = L + S::c_Vb;
+    for (int idx = th.tid; idx < C * N; idx += NT) { JCt[idx] = real_t(0.0); Yt[idx] = real_t(0.0); }
+    DWBC_SYNC();
+    for (int a = 0; a < nc; a++)
+        point_jacobian<N, NB, NT>(th, L + S::Rw0, L + S::pw, L + S::aw, topo, nb, su.c_link[act_c[a]], L + S::Pc + a * 3, JCt, 1, 6 * a, 6, 0, C);
+    DWBC_SYNC();
+    if (k > 0) internal_wrench_basis<N, NT>(th, L + S::Pc, JCt, Vb);  // the only later reader of J_C
+    DWBC_SYNC();
+    const unsigned long long cm0 = nc > 0 ? su.c_dofmask[act_c[0]] : 0ull, cm1 = nc > 1 ? su.c_dofmask[act_c[1]] : 0ull;
+    static_assert(C == 12, "two 6D contacts");
+    LANES {
+        real_t yc[C];
+#pragma unroll
+        for (int p = 0; p < C; p++) yc[p] = real_t(0.0);
+#pragma unroll
+        for (int ib = 0; ib < N; ib += 3) {  // one uniform branch per 3 columns and contact: the zero columns of J_C are skipped
+            if ((cm0 >> ib) & 7) {
+#pragma unroll
+                for (int i = ib; i < ib + 3 && i < N; i++)
+#pragma unroll
+                    for (int p = 0; p < 6; p++) yc[p] += JCt[i * C + p] * LV(s)[i];
+            }
+            if ((cm1 >> ib) & 7) {
+#pragma unroll
+                for (int i = ib; i < ib + 3 && i < N; i++)
+#pragma unroll
+                    for (int p = 6; p < C; p++) yc[p] += JCt[i * C + p] * LV(s)[i];
+            }
+        }
+        if (lane < N) {
+#pragma unroll
+            for (int p = 0; p < C; p++) Yt[lane * C + p] = yc[p];
+        }
+    }
+    DWBC_SYNC();
+    // J A^-1 J^T = Y J_C^T in a C x C block, zero outside cd x cd (operand layout of the tile: see stage 1 of the cycle)
+#if !defined(DWBC_HOST_EMU)
+    if constexpr (sizeof(real_t) == 8) {
+        typedef double lc_d4 __attribute__((ext_vector_type(4)));
+        const int li = lane & 15, lk = lane >> 4;
+        lc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s_ = 0; s_ < (N + 3) / 4; s_++) {
+            const int c = 4 * s_ + lk;
+            const bool in = c < N;
+            const int cc = in ? c : N - 1;
+            real_t av = Yt[cc * C + (li < C ? li : 0)], bv = JCt[cc * C + (li < C ? li : 0)];
+            av = in ? av : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        }
+        if (li < C) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) L[S::c_s2 + (lk + 4 * r) * C + li] = acc[r];
+        }
+    } else
+#endif
+    for (int idx = th.tid; idx < C * C; idx += NT) {
+        const int i = idx / C, j = idx - i * C;
+        real_t a4[4] = {real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0)};
+        if (i < cd && j < cd) {
+#pragma unroll
+            for (int c = 0; c < N; c++) a4[c & 3] += Yt[c * C + i] * JCt[c * C + j];
+        }
+        L[S::c_s2 + idx] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+    }
+    if (cd > 0) {
+        if (!spd_inverse_small(L + S::c_s2, C, cd, Lam, C, L + S::c_s1)) st_contact = 0;  // Lambda_c (wbd.cpp:115)
+    }
+    DWBC_SYNC();
+    // Jbar^T = Lambda_c J A^-1 (wbd.cpp:116) over J_C; the columns of A^-1 are dead after this
+    LANES {
+        real_t yc[C], jb[C];
+        const int col = lane < N ? lane : 0;
+#pragma unroll
+        for (int p = 0; p < C; p++) yc[p] = Yt[col * C + p];
+        lds_rows_dot<C, C, C, 4, 0, false>(Lam, yc, jb);
+#pragma unroll
+        for (int p = 0; p < C; p++)
+            if (lane < N && p < cd) JbT[p * N + lane] = jb[p];
+    }
+    DWBC_SYNC();
+    mv_n<NT>(th, L + S::PC, JbT, N, L + S::G, cd, N);  // P_C = Jbar^T G (wbd.cpp:192)
+    DWBC_SYNC();
+
+    // ================= NwJw from the closed-form internal-wrench basis (see dwbc_cycle2.h): NwJw = Vb G^-1 X^T, X = S^-1 JV =================
+    if (k > 0) {
+        static_assert(kMaxActiveContacts == 2, "k in {0, 6}");
+        constexpr int K6 = 6;
+        for (int idx = th.tid; idx < K6 * K6; idx += NT) {
+            const int i = idx / 6, j = idx - i * 6;
+            real_t acc = real_t(0.0);
+            _Pragma("unroll 8")
+            for (int c = 0; c < M; c++) acc += JbT[i * N + 6 + c] * Vb[c * K6 + j];
+            L[S::c_s2 + idx] = acc;
+        }
+        real_t *JV = L + S::c_s2, *Gi = L + S::c_s2 + 36, *Bm = L + S::c_s2 + 72, *Sm6 = L + S::c_s2 + 108;  // 4 x (6 x 6) in C * C
+        mm_tn<NT>(th, Gi, K6, Vb, K6, Vb, K6, K6, M, K6);                  // G = Vb^T Vb
+        DWBC_SYNC();
+        spd_inverse_small(Gi, K6, K6, Gi, K6, L + S::c_s1);                // G^-1
+        mm_nn<NT>(th, Bm, K6, JV, K6, Gi, K6, K6, K6, K6);                 // B = JV G^-1
+        DWBC_SYNC();
+        mm_nt<NT>(th, Sm6, K6, Bm, K6, JV, K6, K6, K6, K6);                // S = B JV^T (SPD)
+        DWBC_SYNC();
+        if (!spd_inverse_small(Sm6, K6, K6, Sm6, K6, L + S::c_s1)) st_contact = 0;
+        mm_nn<NT>(th, Bm, K6, Sm6, K6, JV, K6, K6, K6, K6);                // X = S^-1 JV
+        DWBC_SYNC();
+        mm_nt<NT>(th, JV, K6, Gi, K6, Bm, K6, K6, K6, K6);                 // G^-1 X^T (JV is dead)
+        DWBC_SYNC();
+        mm_nn<NT>(th, L + S::NwJw, K6, Vb, K6, JV, K6, M, K6, K6);         // NwJw = Vb (G^-1 X^T)
+        DWBC_SYNC();
+    }
+
+    // ================= the wrench maps of [tau_in | NwJw] and the QP (dwbc.cpp:1458-1517) =================
+    const io_t *tin_g = rio.tau_in + (size_t)inst * M;
+    real_t *tin = L + S::t_in, *FN = L + S::fn, *WM = L + S::wm, *fv = L + S::t_fv;
+    for (int i = th.tid; i < M; i += NT) tin[i] = (real_t)tin_g[i];
+    DWBC_SYNC();
+    const int ncol = 1 + k;
+    for (int idx = th.tid; idx < cd * FLD; idx += NT) {
+        const int i = idx / FLD, col = idx - i * FLD;
+        real_t acc = real_t(0.0);
+        if (col < ncol) {
+            const real_t *rhs = col == 0 ? tin : L + S::NwJw + (col - 1);
+            const int rs = col == 0 ? 1 : 6;
+            _Pragma("unroll 8")
+            for (int c = 0; c < M; c++) acc += JbT[i * N + 6 + c] * rhs[c * rs];
+        }
+        FN[idx] = acc;
+    }
+    DWBC_SYNC();
+    // contact-local frames for the cone rows: WM = A_rot FN, fv = A_rot (FN[:, 0] - P_C), A_rot = blockdiag(R_a^T, R_a^T)
+    for (int idx = th.tid; idx < cd * FLD; idx += NT) {
+        const int i = idx / FLD, col = idx - i * FLD;
+        const int a = i / 6, h = (i % 6) / 3, x = i % 3;
+        const real_t *R = L + S::Rc + a * 9;
+        const real_t *src = FN + (6 * a + 3 * h) * FLD + col;
+        const real_t v = R[x] * src[0] + R[3 + x] * src[FLD] + R[6 + x] * src[2 * FLD];
+        WM[i * WLD + col] = v;
+        if (col == 0) {
+            const real_t *pc3 = L + S::PC + 6 * a + 3 * h;
+            fv[i] = v - (R[x] * pc3[0] + R[3 + x] * pc3[1] + R[6 + x] * pc3[2]);
+        }
+    }
+    DWBC_SYNC();
+    int st_redis = 1;
+    real_t xq[6] = {real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0)};
+    if (k > 0 && st_contact) {
+        const int nlim = su.has_tau_lim ? 2 * M : 0, ncone = 10 * nc;
+        QpResult qres;
+        PL(real_t, sfin);
+        // x = c (k), H = I: rows [NwJw] against the torque limits, cone(WM[:, 1:]) against cone(fv); no second block
+        qp_rows_and_solve<N, NB, 0>(su, L, nlim, ncone, act_c[0], act_c[1], L + S::NwJw, 6, k, L + S::NwJw, 6, 0, real_t(1.0), WM + 1, WLD, WM + 1, WLD,
+                                    fv, tin, k, su.qp_max_iter_contact, qres, L + S::qp_V, L + S::qp_x, nullptr, nullptr, kQpFeasTol, sfin);
+        if (qres.status) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) xq[j] = j < k ? L[S::qp_x + j] : real_t(0.0);
+        } else {
+            st_redis = 0;  // dwbc.cpp:1553-1559: zero torque
+        }
+    }
+
+    // ================= outputs =================
+    const bool ok = st_contact && st_redis;
+    io_t *tau = rio.tau + (size_t)inst * M;
+    for (int i = th.tid; i < M; i += NT) {
+        real_t c = real_t(0.0);
+        if (k > 0 && ok) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) c += L[S::NwJw + i * 6 + j] * xq[j];  // NwJw c (dwbc.cpp:1549)
+        }
+        tau[i] = c;
+    }
+    io_t *cf = rio.cf + (size_t)inst * 6;
+    for (int j = th.tid; j < 6; j += NT) {
+        real_t v = real_t(0.0);
+#pragma unroll
+        for (int a = 0; a < 6; a++) v = (a == j) ? xq[a] : v;
+        cf[j] = ok ? v : real_t(0.0);
+    }
+    // getContactForce(tau) = Jbar[:, 6:] tau - P_C (wbd.cpp:268-271) for tau_in and for tau_in + NwJw c: columns of FN
+    io_t *wr = rio.wrench + (size_t)inst * 24;
+    for (int i = th.tid; i < 12; i += NT) {
+        real_t w0 = real_t(0.0), w1 = real_t(0.0);
+        if (i < cd && st_contact) {
+            w0 = FN[i * FLD] - L[S::PC + i];
+            w1 = w0;
+#pragma unroll
+            for (int j = 0; j < 6; j++) w1 += (j < k) ? FN[i * FLD + 1 + j] * xq[j] : real_t(0.0);
+        }
+        wr[i] = w0;
+        wr[12 + i] = w1;
+    }
+    if (th.tid == 0) rio.status[inst] = ok ? 1 : 0;
+}
+
+}  // namespace dwbc

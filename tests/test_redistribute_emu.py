@@ -1,0 +1,92 @@
+"""not-gpu: the redistribution kernel for a caller-supplied torque (libdwbc_amd/csrc/dwbc_redistribute.h) in host emulation
+(tests/emu/emu_redist.cpp: one "thread" per workgroup, LDS NaN-poisoned before every instance) against the numpy restatement.
+
+Inputs and bars: tests/redist_cases.py (states of synth_batch seed 7, tau_in = the restatement's full-cycle torque pushed along the
+contact null space by d = 10 N(0, I6)); 1e-6 Nm on the torque and on DWBC_REDIST_CF . NwJw, 1e-5 N on both wrench rows."""
+import numpy as np
+import pytest
+
+from tests import cases
+from tests import redist_cases as rc
+from tests.emu.emu_redist import EmuRedist
+
+B = 32
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM)
+
+
+@pytest.mark.parametrize("yaw", [False, True], ids=["flat", "yaw"])
+@pytest.mark.parametrize("mode", ["LR", "mixed"])
+def test_emulation_matches_restatement(emu, yaw, mode):
+    ref = rc.state_set(B, yaw, mode)
+    rc.check_premises(ref)
+    got = emu.run(ref["q"], ref["flags"], ref["tau_in"])
+    rc.compare(got, ref)
+
+
+def test_feasible_input_is_left_alone(emu):
+    """tau_in = the cycle's own torque: nothing to redistribute, the correction is zero and both wrench rows are the same wrench"""
+    ref = rc.state_set(B, False, "LR")
+    got = emu.run(ref["q"], ref["flags"], ref["tau_feasible"])
+    assert (got["status"] == 1).all()
+    assert np.abs(got["tau"]).max() <= 1e-6
+    assert (got["wrench"][:, 0] == got["wrench"][:, 1]).all() and np.abs(got["wrench"][:, 0]).max(axis=1).min() > 100.0
+    # and the first row is getContactForce(tau_in) of the restatement
+    cyc = rc._cycle()
+    for b in range(4):
+        _, _, _, w, _ = rc.redistribute_ref(cyc, ref["q"][b], ref["flags"][b], ref["tau_feasible"][b])
+        assert np.abs(got["wrench"][b, 0] - w[0]).max() <= rc.TOL_WRENCH
+
+
+def test_single_support_and_no_contact(emu):
+    ref = rc.state_set(B, True, "mixed")
+    flags = ref["flags"].copy()
+    flags[::5] = 0  # every fifth instance in the air
+    got = emu.run(ref["q"], flags, ref["tau_in"])
+    nact = flags.sum(axis=1)
+    assert (nact == 0).any() and (nact == 1).any() and (nact == 2).any()
+    assert (got["status"] == np.where(nact == 2, ref["status"], 1)).all()
+    single, free = nact == 1, nact == 0
+    # single support (k = 0): zero torque, status 1, the wrench of tau_in still evaluated (six entries, both rows)
+    assert np.abs(got["tau"][single]).max() == 0.0 and np.abs(got["cf"][single]).max() == 0.0
+    cyc = rc._cycle()
+    for b in np.nonzero(single)[0]:
+        _, _, _, w, _ = rc.redistribute_ref(cyc, ref["q"][b], flags[b], ref["tau_in"][b])
+        assert np.abs(w[0, :6]).max() > 1.0 and np.abs(w[0, 6:]).max() == 0.0
+        assert np.abs(got["wrench"][b, 0] - w[0]).max() <= rc.TOL_WRENCH and (got["wrench"][b, 1] == got["wrench"][b, 0]).all()
+    # no active contact: zeros, status 1
+    for k in ("tau", "cf", "wrench"):
+        assert np.abs(got[k][free]).max() == 0.0, k
+
+
+def test_more_than_two_flags_fail_the_instance():
+    e4 = EmuRedist(cases.URDF, cases.CONTACTS_4, cases.TAU_LIM)
+    ref = rc.state_set(B, False, "LR")
+    flags = np.zeros((B, 4), np.uint8)
+    flags[:, :2] = 1
+    flags[1::2, 2] = 1  # a third flag on every other instance
+    got = e4.run(ref["q"], flags, ref["tau_in"])
+    three = flags.sum(axis=1) == 3
+    assert (got["status"][three] == 0).all() and (got["status"][~three] == ref["status"][~three]).all()
+    for k in ("tau", "cf", "wrench"):
+        assert np.abs(got[k][three]).max() == 0.0, k
+    okm = ~three & (ref["status"] == 1)
+    assert np.abs(got["tau"][okm] - ref["tau"][okm]).max() <= rc.TOL_TAU
+
+
+def test_task_levels_play_no_part():
+    """a set-up that carries task levels (a cycle batch's, the facade's) gives bit-identical answers; no torque limit: cone rows only"""
+    ref = rc.state_set(B, False, "LR")
+    plain = EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM).run(ref["q"], ref["flags"], ref["tau_in"])
+    tasked = EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM, tasks=cases.TASKS_2LEVEL).run(ref["q"], ref["flags"], ref["tau_in"])
+    for k in ("tau", "cf", "wrench", "status"):
+        assert (plain[k] == tasked[k]).all(), k
+    nolim = EmuRedist(cases.URDF, cases.CONTACTS_2, None).run(ref["q"], ref["flags"], ref["tau_in"])
+    assert (nolim["status"] == 1).all() and np.isfinite(nolim["tau"]).all()
+
+
+def test_lds_map_is_in_the_compact_class(emu):
+    assert emu.lds_bytes() <= 20480  # eight workgroups per CU
