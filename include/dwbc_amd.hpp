@@ -623,7 +623,7 @@ class RobotData {
     }
     double sent_time_ = -1.0e300;
     void reduced_on() { if (!reduced_) { reduced_ = true; dirty_ = true; } }
-    int diag_[96] = {0};
+    std::vector<int> diag_ = std::vector<int>(4, 0);  // DWBC_DIAG of the last solve (sized by the library in refresh()); the stage status words come first
     Vec tau_contact_final_;
 
     int device_ = 0;
@@ -670,7 +670,8 @@ class RobotData {
         torque_grav_.assign(tau.begin(), tau.begin() + m);
         torque_task_.assign(tau.begin() + m, tau.begin() + 2 * m);
         tau_contact_final_.assign(tau.begin() + 2 * m, tau.end());
-        dwbc_batch_get(batch_, DWBC_DIAG, diag_, sizeof(int) * 90);
+        diag_.resize(dwbc_batch_field_bytes(batch_, DWBC_DIAG) / sizeof(int));
+        dwbc_batch_get(batch_, DWBC_DIAG, diag_.data(), diag_.size() * sizeof(int));
         if (general_) {
             wrench_.assign(dwbc_batch_field_bytes(batch_, DWBC_WRENCH) / 8, 0.0);
             dwbc_batch_get(batch_, DWBC_WRENCH, wrench_.data(), wrench_.size() * 8);

@@ -106,6 +106,27 @@ enum dwbc_field {
     DWBC_J_I_NC = 63,     /* (6, n-12) J_I_nc_, row stride n - 12, zero beyond nc_dof */
     DWBC_J_I_NC_INV_T = 64 /* (6, n-12) J_I_nc_inv_T */
 };
+/* the table behind the enum, one row per field (libdwbc_amd/csrc/dwbc_fields.h), for a caller that sizes or types its buffers from the
+ * library instead of from the comments above: the sizes a shape depends on, and what a row says for them */
+enum { DWBC_ELEM_F64 = 0, DWBC_ELEM_I32 = 1, DWBC_ELEM_U8 = 2 };
+typedef struct dwbc_field_dims {
+    int n;           /* dwbc_model_system_dof */
+    int n_contacts;  /* registered contacts */
+    int fstar_total; /* dwbc_batch_fstar_size */
+    int max_active;  /* dwbc_batch_max_active_contacts */
+} dwbc_field_dims;
+typedef struct dwbc_field_info {
+    int id;           /* enum dwbc_field */
+    const char *name; /* as the Python layer spells it: "in_q", "A_inv_N_C", "Lambda_c", ... */
+    int dtype;        /* DWBC_ELEM_* */
+    int rank;         /* 0 .. 3 */
+    int dims[3];      /* per instance, row-major; unused entries are 1 */
+    size_t bytes;     /* per instance */
+    int bindable;     /* dwbc_batch_bind_device takes it */
+    int host_mirror;  /* dwbc_batch_host_ptr serves it */
+} dwbc_field_info;
+/* row `index` of the field table for the given sizes; 0 when index is past the end.  Needs no device and no batch. */
+int dwbc_field_describe(int index, const dwbc_field_dims *dims, dwbc_field_info *out);
 
 const char *dwbc_last_error(void);
 int dwbc_device_count(void);

@@ -12,6 +12,16 @@ LIB_PATH = os.path.join(_HERE, "libdwbc_hip_timed.so" if os.environ.get("DWBC_TI
 
 # every symbol include/dwbc_batch.h declares: (name, restype, argtypes)
 _vp, _i, _d, _cp = C.c_void_p, C.c_int, C.c_double, C.c_char_p
+
+
+class FieldDims(C.Structure):  # dwbc_field_dims
+    _fields_ = [("n", _i), ("n_contacts", _i), ("fstar_total", _i), ("max_active", _i)]
+
+
+class FieldInfo(C.Structure):  # dwbc_field_info
+    _fields_ = [("id", _i), ("name", _cp), ("dtype", _i), ("rank", _i), ("dims", _i * 3), ("bytes", C.c_size_t), ("bindable", _i), ("host_mirror", _i)]
+
+
 SYMBOLS = [
     ("dwbc_last_error", _cp, []),
     ("dwbc_device_count", _i, []),
@@ -57,6 +67,7 @@ SYMBOLS = [
     ("dwbc_batch_time_solves", _i, [_vp, C.c_uint, _i, C.POINTER(C.c_float)]),
     ("dwbc_batch_get", _i, [_vp, _i, _vp, C.c_size_t]),
     ("dwbc_batch_field_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_field_describe", _i, [_i, C.POINTER(FieldDims), C.POINTER(FieldInfo)]),
     ("dwbc_batch_launch_info", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("dwbc_batch_kernel_name", C.c_char_p, [_vp]),
     # generic hierarchical-QP class + LQP configurator

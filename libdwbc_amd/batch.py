@@ -26,16 +26,19 @@ TASK_LINK_POSITION, TASK_LINK_POSITION_COM_FRAME, TASK_LINK_POSITION_CUSTOM_FRAM
 TASK_LINK_ROTATION, TASK_LINK_ROTATION_CUSTOM_FRAME = 6, 7
 SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
 
-# field ids of include/dwbc_batch.h
-FIELDS = dict(
-    in_q=0, in_contact=1, in_fstar=2, in_torque=3, tau=10, wrench=11, status=12, diag=13,
-    redist_tau=14, redist_cf=15, redist_wrench=16, redist_status=17,
-    tau_grav=20, tau_task=21, tau_contact=22, tau_total=23,
-    A=30, A_inv=31, J_C=32, Lambda_c=33, J_C_INV_T=34, A_inv_N_C=35, W_inv=36, NwJw=37, G=38, P_C=39,
-    link_R=40, link_p=41, fstar_qp=42, contact_qp=43, cf_redis=44, J_task=45, Lambda_task=46, J_kt=47, qp_viol=48,
-    CMM=50, com=51, com_inertia=52, J_com=53, B=54, link_v=55, link_w=56, contact_pos=57, contact_rot=58, zmp=59,
-    A_R=60, A_R_inv=61, G_R=62, J_I_nc=63, J_I_nc_inv_T=64,
-)
+
+def describe(index, n, n_contacts, fstar_total, max_active):
+    """row `index` of the library's field table (libdwbc_amd/csrc/dwbc_fields.h) for these sizes, None past the end"""
+    info = _lib.FieldInfo()
+    ok = _lib.load().dwbc_field_describe(index, C.byref(_lib.FieldDims(n, n_contacts, fstar_total, max_active)), C.byref(info))
+    return info if ok else None
+
+
+# name -> field id of include/dwbc_batch.h, and name -> row of the table: read from the library once
+FIELDS, _ROW = {}, {}
+while (_r := describe(len(_ROW), 0, 0, 0, 0)) is not None:
+    FIELDS[_r.name.decode()], _ROW[_r.name.decode()] = _r.id, len(_ROW)
+_DTYPES = (np.float64, np.int32, np.uint8)  # DWBC_ELEM_*
 
 
 class DwbcError(RuntimeError):
@@ -294,14 +297,11 @@ class Batch:
         """numpy view of the page-locked host mirror of an input field ("in_q", "in_contact", "in_fstar", "in_torque"): fill it in place and
         pass it to set_state / set_contact / set_fstar_all / set_torque_input -- the host-side copy is skipped, the upload is one
         asynchronous transfer"""
-        shape = (self.B,) + tuple(self._SHAPES[field](self))
-        dt = np.uint8 if field == "in_contact" else np.float64
+        shape, dt, nbytes = self._layout(field)
         p = self._L.dwbc_batch_host_ptr(self._h, FIELDS[field])
         if not p:
             raise DwbcError(f"{field} has no host mirror yet (add the contacts / tasks first)")
-        n = int(np.prod(shape))
-        buf = (C.c_uint8 * n if dt == np.uint8 else C.c_double * n).from_address(p)
-        return np.frombuffer(buf, dtype=dt).reshape(shape)
+        return np.frombuffer((C.c_uint8 * nbytes).from_address(p), dtype=dt).reshape(shape)
 
     # ---- zero-copy device plumbing (torch owns the memory / stream)
     def bind_tensor(self, field, tensor):
@@ -364,30 +364,16 @@ class Batch:
     def kernel_name(self):
         return self._L.dwbc_batch_kernel_name(self._h).decode()
 
-    _SHAPES = dict(
-        tau=lambda s: (3, s.m), wrench=lambda s: (6 * s.max_active_contacts,), status=lambda s: (), diag=lambda s: (90,),
-        tau_grav=lambda s: (s.m,), tau_task=lambda s: (s.m,), tau_contact=lambda s: (s.m,), tau_total=lambda s: (s.m,),
-        A=lambda s: (s.n, s.n), A_inv=lambda s: (s.n, s.n), A_inv_N_C=lambda s: (s.n, s.n), J_C=lambda s: (12, s.n),
-        J_C_INV_T=lambda s: (12, s.n), Lambda_c=lambda s: (144,), W_inv=lambda s: (s.m, s.m), NwJw=lambda s: (s.m, 6),
-        G=lambda s: (s.n,), P_C=lambda s: (12,), link_R=lambda s: (48, 3, 3), link_p=lambda s: (48, 3),
-        fstar_qp=lambda s: (4, 6), contact_qp=lambda s: (4, 6), cf_redis=lambda s: (6,), J_task=lambda s: (4, 6 * s.n),
-        Lambda_task=lambda s: (4, 36), J_kt=lambda s: (4, s.m * 6), qp_viol=lambda s: (5,),
-        CMM=lambda s: (6, s.n), com=lambda s: (3,), com_inertia=lambda s: (3, 3), J_com=lambda s: (6, s.n),
-        B=lambda s: (s.n,), link_v=lambda s: (48, 3), link_w=lambda s: (48, 3),
-        contact_pos=lambda s: (2, 3), contact_rot=lambda s: (2, 3, 3), zmp=lambda s: (3, 3),
-        A_R=lambda s: (24, 24), A_R_inv=lambda s: (24, 24), G_R=lambda s: (24,), J_I_nc=lambda s: (6, s.n - 12), J_I_nc_inv_T=lambda s: (6, s.n - 12),
-        in_q=lambda s: (s.n + 1,), in_contact=lambda s: (s.n_contacts,), in_fstar=lambda s: (s.fstar_size,), in_torque=lambda s: (s.m,),
-        redist_tau=lambda s: (s.m,), redist_cf=lambda s: (6,), redist_wrench=lambda s: (2, 12), redist_status=lambda s: (),
-    )
+    def _layout(self, field):
+        """(B, ...) shape, element type and bytes of a field of this batch, from the library's table"""
+        r = describe(_ROW[field], self.n, self.n_contacts, self.fstar_size, self.max_active_contacts)
+        return (self.B,) + tuple(r.dims[: r.rank]), _DTYPES[r.dtype], self.B * r.bytes
 
     def get(self, field):
-        fid = FIELDS[field]
-        shape = (self.B,) + tuple(self._SHAPES[field](self))
-        dt = np.int32 if field in ("status", "diag", "redist_status") else (np.uint8 if field == "in_contact" else np.float64)
+        shape, dt, nbytes = self._layout(field)
         out = np.zeros(shape, dtype=dt)
-        nbytes = self._L.dwbc_batch_field_bytes(self._h, fid)
-        assert nbytes == out.nbytes, (field, nbytes, out.nbytes)
-        _check(self._L.dwbc_batch_get(self._h, fid, out.ctypes.data, out.nbytes))
+        assert nbytes == out.nbytes == self._L.dwbc_batch_field_bytes(self._h, FIELDS[field]), (field, nbytes, out.nbytes)
+        _check(self._L.dwbc_batch_get(self._h, FIELDS[field], out.ctypes.data, out.nbytes))
         return out
 
     def close(self):

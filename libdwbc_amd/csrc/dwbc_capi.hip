@@ -244,6 +244,59 @@ static dwbc_plan::Request plan_request(const dwbc_batch *b, bool reduced) {
     return q;
 }
 
+namespace fld = dwbc_fields;
+using dwbc::Buf;
+
+static dwbc_field_dims field_dims(const dwbc_batch *b) { return dwbc_field_dims{b->n, b->su.n_contacts, b->su.fstar_total, b->max_active}; }
+
+int dwbc_field_describe(int index, const dwbc_field_dims *dims, dwbc_field_info *out) {
+    if (index < 0 || index >= fld::kRowCount || !dims || !out) return 0;
+    const fld::Row &r = fld::kRows[index];
+    *out = dwbc_field_info{r.id, r.name, r.type, r.shape.rank, {1, 1, 1}, fld::elements(r, *dims) * fld::item_size(r.type), (r.flags & fld::kBindable) != 0, (r.flags & fld::kMirror) != 0};
+    for (int i = 0; i < r.shape.rank; i++) out->dims[i] = fld::extent(r.shape.dim[i], *dims);
+    return 1;
+}
+
+size_t dwbc_batch_field_bytes(const dwbc_batch *b, int field) {
+    const fld::Row *r = fld::find(field);
+    return r ? (size_t)b->B * fld::elements(*r, field_dims(b)) * fld::item_size(r->type) : 0;
+}
+
+// ---- the buffer slots (dwbc_batch::buf).  The batch's device is current in all three.
+static void release(Buf &u) {  // a bound buffer is let go of, an owned one freed
+    if (u.own) (void)hipFree(u.d);
+    u.d = nullptr; u.own = false; u.bytes = 0;
+}
+// an owned buffer of this size (a bound one stays: the caller sized it); a fresh one is marked for upload if the slot has a mirror
+static int ensure(Buf &u, size_t bytes) {
+    if (u.bound() || (u.d && u.bytes == bytes)) return 1;
+    release(u);
+    HIP_OK(hipMalloc(&u.d, bytes));
+    u.own = true; u.bytes = bytes; u.dirty = !u.h.empty();
+    return 1;
+}
+static int ensure_field(dwbc_batch *b, int field) { return ensure(b->buf[fld::find(field)->idx], dwbc_batch_field_bytes(b, field)); }
+// the mirror of a slot to its own device buffer (sized like the mirror) if it is newer; *queued: a copy out of page-locked memory is in
+// flight behind this (mark_upload)
+static int send(dwbc_batch *b, int slot, bool *queued) {
+    Buf &u = b->buf[slot];
+    if (!u.h.empty() && !u.bound()) {
+        if (!ensure(u, u.h.size())) return 0;
+        if (u.dirty) {
+            HIP_OK(hipMemcpyAsync(u.d, u.h.data(), u.h.size(), hipMemcpyHostToDevice, b->stream));
+            *queued = *queued || u.h.pinned;
+        }
+    }
+    u.dirty = false;
+    return 1;
+}
+static int mark_upload(dwbc_batch *b) {
+    if (!b->ev_upload) HIP_OK(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(b->ev_upload, b->stream));
+    b->upload_pending = true;
+    return 1;
+}
+
 dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype) {
     if (!m || B < 1) { g_err = "bad arguments"; return nullptr; }
     if (dtype != DWBC_F64 && dtype != DWBC_F32) { g_err = "dtype must be DWBC_F64 or DWBC_F32"; return nullptr; }
@@ -293,42 +346,20 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     if ((e = hipMalloc(&b->d_topo, topo.size() * sizeof(int))) != hipSuccess) return bad("hipMalloc", e);
     if ((e = hipMemcpy(b->d_body, body.data(), body.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return bad("hipMemcpy", e);
     if ((e = hipMemcpy(b->d_topo, topo.data(), topo.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return bad("hipMemcpy", e);
-    if ((e = hipMalloc(&b->d_q, (size_t)B * (b->n + 1) * sizeof(double))) != hipSuccess) return bad("hipMalloc", e);
-    b->own_q = true;
-    if ((e = hipMalloc(&b->d_tau, (size_t)B * 3 * b->m * sizeof(double))) != hipSuccess) return bad("hipMalloc", e);
-    b->own_tau = true;
-    if ((e = hipMalloc(&b->d_wrench, (size_t)B * 12 * sizeof(double))) != hipSuccess) return bad("hipMalloc", e);
-    b->own_wrench = true;
-    if ((e = hipMalloc(&b->d_status, (size_t)B * sizeof(int))) != hipSuccess) return bad("hipMalloc", e);
-    b->own_status = true;
-    if ((e = hipMalloc(&b->d_diag, (size_t)B * DG_COUNT * sizeof(int))) != hipSuccess) return bad("hipMalloc", e);
-    hipMemset(b->d_diag, 0, (size_t)B * DG_COUNT * sizeof(int));
-    hipMemset(b->d_status, 0, (size_t)B * sizeof(int));
-    b->h_q.assign((size_t)B * (b->n + 1), 0.0);
-    b->h_tau_in.assign((size_t)B * b->m, 0.0);
+    for (const int f : {DWBC_IN_Q, DWBC_TAU, DWBC_WRENCH, DWBC_STATUS, DWBC_DIAG})
+        if (!ensure_field(b, f)) { dwbc_batch_destroy(b); return nullptr; }
+    hipMemset(b->buf[fld::kDiag].d, 0, b->buf[fld::kDiag].bytes);
+    hipMemset(b->buf[fld::kStatus].d, 0, b->buf[fld::kStatus].bytes);
+    b->buf[fld::kQ].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_Q));
+    b->buf[fld::kTauIn].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_TORQUE));
     return b;
 }
 
 void dwbc_batch_destroy(dwbc_batch *b) {
     if (!b) return;
     hipSetDevice(b->device);
-    if (b->own_q) hipFree(b->d_q);
-    if (b->d_qdot) hipFree(b->d_qdot);
+    for (Buf &u : b->buf) release(u);
     if (b->f_body) hipFree(b->f_body);
-    if (b->d_traj) hipFree(b->d_traj);
-    if (b->d_ctime) hipFree(b->d_ctime);
-    if (b->d_custom) hipFree(b->d_custom);
-    if (b->own_fstar) hipFree(b->d_fstar);
-    if (b->own_flags) hipFree(b->d_flags);
-    if (b->own_tau) hipFree(b->d_tau);
-    if (b->own_wrench) hipFree(b->d_wrench);
-    if (b->own_status) hipFree(b->d_status);
-    if (b->own_tau_in) hipFree(b->d_tau_in);
-    if (b->own_rd_tau) hipFree(b->d_rd_tau);
-    if (b->own_rd_cf) hipFree(b->d_rd_cf);
-    if (b->own_rd_wrench) hipFree(b->d_rd_wrench);
-    if (b->own_rd_status) hipFree(b->d_rd_status);
-    hipFree(b->d_diag);
     hipFree(b->d_total);
     for (int l = 0; l < kMaxLevels; l++) hipFree(b->d_jacc[l]);
     hipFree(b->d_jacc_status);
@@ -349,33 +380,32 @@ int dwbc_batch_add_contact(dwbc_batch *b, int link, int contact_type, const doub
     std::string err;
     const int i = setup_add_contact(b->su, link, contact_type, point, lx, ly, mu, mu_z, err);
     if (i < 0) { fail(err); return -1; }
-    b->h_flags.assign((size_t)b->B * b->su.n_contacts, 0);
-    b->dirty_flags = true;
+    b->buf[fld::kFlags].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_CONTACT));
+    b->buf[fld::kFlags].dirty = true;
     return i;
 }
 
 int dwbc_batch_clear_contacts(dwbc_batch *b) {
     b->su.n_contacts = 0;
-    b->h_flags.clear();
+    b->buf[fld::kFlags].h.clear();
     return 1;
 }
 
 int dwbc_batch_add_task(dwbc_batch *b, int level, int mode, int link, const double point[3]) {
     std::string err;
     if (!setup_add_task(b->su, level, mode, link, point, err)) return fail(err);
-    b->h_fstar.assign((size_t)b->B * b->su.fstar_total, 0.0);
-    b->dirty_fstar = true;
+    b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
+    b->buf[fld::kFstar].dirty = true;
     return 1;
 }
 
 int dwbc_batch_add_custom_task(dwbc_batch *b, int level, int task_dof) {
     std::string err;
     if (!setup_add_custom_task(b->su, level, task_dof, err)) return fail(err);
-    b->h_fstar.assign((size_t)b->B * b->su.fstar_total, 0.0);
-    b->dirty_fstar = true;
-    b->h_custom.assign((size_t)b->B * b->su.n_custom * kMaxTaskDof * b->n, 0.0);
-    if (b->d_custom) { hipFree(b->d_custom); b->d_custom = nullptr; }
-    b->dirty_custom = true;
+    b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
+    b->buf[fld::kFstar].dirty = true;
+    b->buf[fld::kCustom].h.assign((size_t)b->B * b->su.n_custom * kMaxTaskDof * b->n * sizeof(double));
+    b->buf[fld::kCustom].dirty = true;
     return 1;
 }
 
@@ -387,8 +417,9 @@ int dwbc_batch_set_custom_task(dwbc_batch *b, int level, const double *fstar, co
     if (fstar && !dwbc_batch_set_fstar(b, level, fstar)) return 0;
     const int t = b->su.t_dof[level], n = b->n, ns = b->su.n_custom;
     const size_t stride = (size_t)kMaxTaskDof * n;
-    for (int i = 0; i < b->B; i++) memcpy(&b->h_custom[((size_t)i * ns + slot) * stride], J + (size_t)i * t * n, sizeof(double) * t * n);
-    b->dirty_custom = true;
+    double *hc = b->buf[fld::kCustom].h.as<double>();
+    for (int i = 0; i < b->B; i++) memcpy(hc + ((size_t)i * ns + slot) * stride, J + (size_t)i * t * n, sizeof(double) * t * n);
+    b->buf[fld::kCustom].dirty = true;
     return 1;
 }
 
@@ -397,13 +428,13 @@ int dwbc_batch_clear_tasks(dwbc_batch *b) {
     b->su.has_com_task = 0;
     b->su.n_custom = 0;
     for (int l = 0; l < kMaxLevels; l++) b->su.t_custom_slot[l] = -1;
-    b->h_custom.clear();
+    b->buf[fld::kCustom].h.clear();
     setup_fstar_layout(b->su);
-    b->h_fstar.clear();
+    b->buf[fld::kFstar].h.clear();
     b->su.n_traj = 0;
     for (int l = 0; l < kMaxLevels; l++)
         for (int j = 0; j < kMaxTaskLinks; j++) b->su.t_traj_slot[l][j] = -1;
-    b->h_traj.clear();
+    b->buf[fld::kTraj].h.clear();
     return 1;
 }
 
@@ -419,6 +450,7 @@ int dwbc_batch_set_task_gain(dwbc_batch *b, int level, int link_index, const dou
 int dwbc_batch_set_trajectory(dwbc_batch *b, int level, int link_index, const double *traj) {
     if (level < 0 || level >= b->su.n_levels || link_index < 0 || link_index >= b->su.t_nlinks[level]) return fail("bad task level / link index");
     int &slot = b->su.t_traj_slot[level][link_index];
+    HostBytes &ht = b->buf[fld::kTraj].h;
     if (!traj) {  // back to SetTaskSpace values for this link (slots of other links keep their place)
         slot = -1;
         return 1;
@@ -430,23 +462,22 @@ int dwbc_batch_set_trajectory(dwbc_batch *b, int level, int link_index, const do
         std::vector<double> h((size_t)b->B * now * kTrajStride, 0.0);
         for (int i = 0; i < b->B; i++)
             for (int sidx = 0; sidx < old; sidx++)
-                memcpy(&h[((size_t)i * now + sidx) * kTrajStride], &b->h_traj[((size_t)i * old + sidx) * kTrajStride], kTrajStride * sizeof(double));
-        b->h_traj.swap(h);
+                memcpy(&h[((size_t)i * now + sidx) * kTrajStride], ht.as<double>() + ((size_t)i * old + sidx) * kTrajStride, kTrajStride * sizeof(double));
+        ht.assign(h.data(), h.size() * sizeof(double));
         slot = old;
         b->su.n_traj = now;
-        if (b->d_traj) { hipFree(b->d_traj); b->d_traj = nullptr; }
     }
     const int ns = b->su.n_traj;
     for (int i = 0; i < b->B; i++)
-        memcpy(&b->h_traj[((size_t)i * ns + slot) * kTrajStride], traj + (size_t)i * kTrajStride, kTrajStride * sizeof(double));
-    b->dirty_traj = true;
+        memcpy(ht.as<double>() + ((size_t)i * ns + slot) * kTrajStride, traj + (size_t)i * kTrajStride, kTrajStride * sizeof(double));
+    b->buf[fld::kTraj].dirty = true;
     return 1;
 }
 
 int dwbc_batch_set_control_time(dwbc_batch *b, const double *t) {
     if (!t) return fail("control time is NULL");
-    b->h_ctime.assign(t, t + b->B);
-    b->dirty_ctime = true;
+    b->buf[fld::kCtime].h.assign(t, (size_t)b->B * sizeof(double));
+    b->buf[fld::kCtime].dirty = true;
     return 1;
 }
 
@@ -471,20 +502,22 @@ static void wait_uploads(dwbc_batch *b) {
 int dwbc_batch_set_state(dwbc_batch *b, const double *q, const double *qdot, const double *qddot) {
     (void)qddot;  // the reference hands it to RBDL's UpdateKinematicsCustom only; nothing on this path reads accelerations
     if (!q) return fail("q is NULL");
-    if (!b->own_q) return fail("q is bound to a device buffer");
+    Buf &uq = b->buf[fld::kQ];
+    if (uq.bound()) return fail("q is bound to a device buffer");
     wait_uploads(b);
-    if (q != b->h_q.data()) memcpy(b->h_q.data(), q, b->h_q.size() * sizeof(double));  // (dwbc_batch_host_ptr: already in place)
-    b->dirty_q = true;
+    if (q != uq.h.as<double>()) memcpy(uq.h.data(), q, uq.h.size());  // (dwbc_batch_host_ptr: already in place)
+    uq.dirty = true;
     if (qdot) {  // B_, link velocities (dump record) and the on-device task reference need it; the torque path does not
-        b->h_qdot.assign(qdot, qdot + (size_t)b->B * b->n);
-        b->dirty_qdot = true;
+        b->buf[fld::kQdot].h.assign(qdot, (size_t)b->B * b->n * sizeof(double));
+        b->buf[fld::kQdot].dirty = true;
     }
     return 1;
 }
 
 int dwbc_batch_set_contact(dwbc_batch *b, const uint8_t *flags) {
     if (b->su.n_contacts == 0) return fail("Contact Constraint size mismatch");  // include/dwbc.h:438-441
-    if (b->d_flags && !b->own_flags) return fail("contact flags are bound to a device buffer");
+    Buf &uf = b->buf[fld::kFlags];
+    if (uf.bound()) return fail("contact flags are bound to a device buffer");
     // the product kernels stack two simultaneous 6D contacts, the general-contact kernel three (the reference: any number,
     // src/dwbc.cpp:445-453); an instance with more than the batch is set up for is refused here instead of failing on the device
     const int ncn = b->su.n_contacts;
@@ -496,8 +529,8 @@ int dwbc_batch_set_contact(dwbc_batch *b, const uint8_t *flags) {
                                           : "more than 2 simultaneously active contacts in one instance: call dwbc_batch_set_max_active_contacts(b, 3) first (3 is the most the device path stacks)");
     }
     wait_uploads(b);
-    if (flags != b->h_flags.data()) memcpy(b->h_flags.data(), flags, b->h_flags.size());
-    b->dirty_flags = true;
+    if (flags != uf.h.data()) memcpy(uf.h.data(), flags, uf.h.size());
+    uf.dirty = true;
     return 1;
 }
 
@@ -511,26 +544,31 @@ int dwbc_batch_set_max_active_contacts(dwbc_batch *b, int n) {
         const dwbc_plan::Request q = plan_request(b, false);
         if (!dwbc_plan::Candidates(q, dwbc_plan::kGc, b->tables, b->n_tables).pick(dwbc_plan::kWideTasks, 0u)) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
     }
-    if (!b->own_wrench) return fail("wrench is bound to a device buffer: set the contact capacity before binding");
+    Buf &uw = b->buf[fld::kWrench];
+    if (uw.bound()) return fail("wrench is bound to a device buffer: set the contact capacity before binding");
     if (n < b->max_active) {  // lowering the capacity: the flags already set must fit it (they were validated against the old one)
         const int ncn = b->su.n_contacts;
-        for (int i = 0; i < b->B && ncn > 0 && !b->h_flags.empty(); i++) {
+        const HostBytes &hf = b->buf[fld::kFlags].h;
+        for (int i = 0; i < b->B && ncn > 0 && !hf.empty(); i++) {
             int on = 0;
-            for (int c = 0; c < ncn; c++) on += b->h_flags[(size_t)i * ncn + c] ? 1 : 0;
+            for (int c = 0; c < ncn; c++) on += hf[(size_t)i * ncn + c] ? 1 : 0;
             if (on > n) return fail("max active contacts: the contact flags of this batch hold an instance with more active contacts than the new capacity");
         }
     }
     HIP_OK(hipSetDevice(b->device));  // (the new buffer must live on the batch's device whatever device is current in the caller's thread)
     HIP_OK(hipStreamSynchronize(b->stream));
     // the new buffer first, the swap only on success: a failed allocation leaves the batch as it was
-    double *nw = nullptr;
-    HIP_OK(hipMalloc(&nw, (size_t)b->B * 6 * n * sizeof(double)));
-    if (hipMemset(nw, 0, (size_t)b->B * 6 * n * sizeof(double)) != hipSuccess) {
+    dwbc_field_dims dims = field_dims(b);
+    dims.max_active = n;
+    const size_t bytes = (size_t)b->B * fld::elements(*fld::find(DWBC_WRENCH), dims) * sizeof(double);
+    void *nw = nullptr;
+    HIP_OK(hipMalloc(&nw, bytes));
+    if (hipMemset(nw, 0, bytes) != hipSuccess) {
         (void)hipFree(nw);
         return fail("max active contacts: hipMemset of the new wrench buffer failed");
     }
-    (void)hipFree(b->d_wrench);
-    b->d_wrench = nw;
+    release(uw);
+    uw.d = nw; uw.own = true; uw.bytes = bytes;
     b->max_active = n;
     return 1;
 }
@@ -538,43 +576,34 @@ int dwbc_batch_max_active_contacts(const dwbc_batch *b) { return b->max_active; 
 
 int dwbc_batch_set_fstar(dwbc_batch *b, int level, const double *fstar) {
     if (level < 0 || level >= b->su.n_levels) return fail("ERROR : task space size overflow");  // src/dwbc.cpp:668-671
-    if (b->d_fstar && !b->own_fstar) return fail("f* is bound to a device buffer");
+    Buf &uf = b->buf[fld::kFstar];
+    if (uf.bound()) return fail("f* is bound to a device buffer");
     const int t = b->su.t_dof[level], off = b->su.fstar_off[level], F = b->su.fstar_total;
     wait_uploads(b);
-    if (fstar != b->h_fstar.data() + off)  // (a caller that filled the mirror in place passes host_ptr + off)
-        for (int i = 0; i < b->B; i++) memcpy(b->h_fstar.data() + (size_t)i * F + off, fstar + (size_t)i * t, sizeof(double) * t);
-    b->dirty_fstar = true;
+    double *hf = uf.h.as<double>();
+    if (fstar != hf + off)  // (a caller that filled the mirror in place passes host_ptr + off)
+        for (int i = 0; i < b->B; i++) memcpy(hf + (size_t)i * F + off, fstar + (size_t)i * t, sizeof(double) * t);
+    uf.dirty = true;
     return 1;
 }
 
 void *dwbc_batch_host_ptr(dwbc_batch *b, int field) {
     wait_uploads(b);  // the caller is about to write into the mirror
-    switch (field) {
-        case DWBC_IN_Q: return b->h_q.empty() ? nullptr : b->h_q.data();
-        case DWBC_IN_CONTACT: return b->h_flags.empty() ? nullptr : b->h_flags.data();
-        case DWBC_IN_FSTAR: return b->h_fstar.empty() ? nullptr : b->h_fstar.data();
-        case DWBC_IN_TORQUE: return b->h_tau_in.empty() ? nullptr : b->h_tau_in.data();
-        default: return nullptr;
-    }
+    const fld::Row *r = fld::find(field);
+    if (!r || !(r->flags & fld::kMirror)) return nullptr;
+    return b->buf[r->idx].h.data();  // (NULL while the field has no size)
 }
 
 int dwbc_batch_bind_device(dwbc_batch *b, int field, void *p) {
     if (!p) return fail("NULL device pointer");
     hipSetDevice(b->device);
-    switch (field) {
-        case DWBC_IN_Q: if (b->own_q) hipFree(b->d_q); b->d_q = (double *)p; b->own_q = false; b->dirty_q = false; return 1;
-        case DWBC_IN_CONTACT: if (b->own_flags) hipFree(b->d_flags); b->d_flags = (unsigned char *)p; b->own_flags = false; b->dirty_flags = false; return 1;
-        case DWBC_IN_FSTAR: if (b->own_fstar) hipFree(b->d_fstar); b->d_fstar = (double *)p; b->own_fstar = false; b->dirty_fstar = false; return 1;
-        case DWBC_TAU: if (b->own_tau) hipFree(b->d_tau); b->d_tau = (double *)p; b->own_tau = false; return 1;
-        case DWBC_WRENCH: if (b->own_wrench) hipFree(b->d_wrench); b->d_wrench = (double *)p; b->own_wrench = false; return 1;
-        case DWBC_STATUS: if (b->own_status) hipFree(b->d_status); b->d_status = (int *)p; b->own_status = false; return 1;
-        case DWBC_IN_TORQUE: if (b->own_tau_in) hipFree(b->d_tau_in); b->d_tau_in = (double *)p; b->own_tau_in = false; b->dirty_tau_in = false; b->tau_in_set = true; return 1;
-        case DWBC_REDIST_TAU: if (b->own_rd_tau) hipFree(b->d_rd_tau); b->d_rd_tau = (double *)p; b->own_rd_tau = false; return 1;
-        case DWBC_REDIST_CF: if (b->own_rd_cf) hipFree(b->d_rd_cf); b->d_rd_cf = (double *)p; b->own_rd_cf = false; return 1;
-        case DWBC_REDIST_WRENCH: if (b->own_rd_wrench) hipFree(b->d_rd_wrench); b->d_rd_wrench = (double *)p; b->own_rd_wrench = false; return 1;
-        case DWBC_REDIST_STATUS: if (b->own_rd_status) hipFree(b->d_rd_status); b->d_rd_status = (int *)p; b->own_rd_status = false; return 1;
-        default: return fail("field cannot be bound");
-    }
+    const fld::Row *r = fld::find(field);
+    if (!r || !(r->flags & fld::kBindable)) return fail("field cannot be bound");
+    Buf &u = b->buf[r->idx];
+    release(u);
+    u.d = p; u.dirty = false;
+    if (field == DWBC_IN_TORQUE) b->tau_in_set = true;
+    return 1;
 }
 
 int dwbc_batch_set_stream(dwbc_batch *b, void *s) { b->stream = (hipStream_t)s; return 1; }
@@ -587,52 +616,10 @@ int dwbc_batch_enable_dump(dwbc_batch *b, int on) {
 }
 
 static int upload_inputs(dwbc_batch *b) {
-    if (b->su.n_contacts > 0 && (!b->d_flags || (b->own_flags && b->flags_alloc != b->su.n_contacts))) {
-        if (b->own_flags && b->d_flags) hipFree(b->d_flags);
-        HIP_OK(hipMalloc(&b->d_flags, (size_t)b->B * b->su.n_contacts));
-        b->own_flags = true;
-        b->flags_alloc = b->su.n_contacts;
-        b->dirty_flags = true;
-    }
-    if (b->su.fstar_total > 0 && (!b->d_fstar || (b->own_fstar && b->fstar_alloc != b->su.fstar_total))) {
-        if (b->own_fstar && b->d_fstar) hipFree(b->d_fstar);
-        HIP_OK(hipMalloc(&b->d_fstar, (size_t)b->B * b->su.fstar_total * sizeof(double)));
-        b->own_fstar = true;
-        b->fstar_alloc = b->su.fstar_total;
-        b->dirty_fstar = true;
-    }
-    if (b->dirty_traj && b->su.n_traj > 0) {
-        if (!b->d_traj) HIP_OK(hipMalloc(&b->d_traj, b->h_traj.size() * sizeof(double)));
-        HIP_OK(hipMemcpyAsync(b->d_traj, b->h_traj.data(), b->h_traj.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        b->dirty_traj = false;
-    }
-    if (b->dirty_custom && b->su.n_custom > 0) {
-        if (!b->d_custom) HIP_OK(hipMalloc(&b->d_custom, b->h_custom.size() * sizeof(double)));
-        HIP_OK(hipMemcpyAsync(b->d_custom, b->h_custom.data(), b->h_custom.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        b->dirty_custom = false;
-    }
-    if (b->dirty_ctime) {
-        if (!b->d_ctime) HIP_OK(hipMalloc(&b->d_ctime, (size_t)b->B * sizeof(double)));
-        HIP_OK(hipMemcpyAsync(b->d_ctime, b->h_ctime.data(), b->h_ctime.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        b->dirty_ctime = false;
-    }
-    const bool qdot_copied = b->dirty_qdot;
-    if (b->dirty_qdot) {
-        if (!b->d_qdot) HIP_OK(hipMalloc(&b->d_qdot, (size_t)b->B * b->n * sizeof(double)));
-        HIP_OK(hipMemcpyAsync(b->d_qdot, b->h_qdot.data(), b->h_qdot.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        b->dirty_qdot = false;
-    }
-    if (b->dirty_q && b->own_q) HIP_OK(hipMemcpyAsync(b->d_q, b->h_q.data(), b->h_q.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (b->dirty_flags && b->own_flags) HIP_OK(hipMemcpyAsync(b->d_flags, b->h_flags.data(), b->h_flags.size(), hipMemcpyHostToDevice, b->stream));
-    if (b->dirty_fstar && b->own_fstar) HIP_OK(hipMemcpyAsync(b->d_fstar, b->h_fstar.data(), b->h_fstar.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    const bool copied = (b->dirty_q && b->own_q) || (b->dirty_flags && b->own_flags) || (b->dirty_fstar && b->own_fstar) || qdot_copied;
-    b->dirty_q = b->dirty_flags = b->dirty_fstar = false;
-    if (copied) {
-        if (!b->ev_upload) HIP_OK(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(b->ev_upload, b->stream));
-        b->upload_pending = true;
-    }
-    return 1;
+    bool queued = false;
+    for (const int slot : {fld::kTraj, fld::kCustom, fld::kCtime, fld::kQdot, fld::kQ, fld::kFlags, fld::kFstar})
+        if (!send(b, slot, &queued)) return 0;
+    return queued ? mark_upload(b) : 1;
 }
 
 // one launch of the cycle: the planner picks the build, whatever its arithmetic type or kind
@@ -654,18 +641,18 @@ static int launch(dwbc_batch *b, bool reduced) {
     }
     BatchIO io{};
     io.B = b->B;
-    io.q = b->d_q;
-    io.qdot = b->d_qdot;
-    io.traj = b->su.n_traj > 0 ? b->d_traj : nullptr;
-    io.ctime = b->d_ctime;
-    io.custom_J = b->su.n_custom > 0 ? b->d_custom : nullptr;
-    io.flags = b->d_flags;
-    io.fstar = b->d_fstar;
-    io.tau = b->d_tau;
-    io.wrench = b->d_wrench;
+    io.q = b->dev<double>(fld::kQ);
+    io.qdot = b->dev<double>(fld::kQdot);
+    io.traj = b->su.n_traj > 0 ? b->dev<double>(fld::kTraj) : nullptr;
+    io.ctime = b->dev<double>(fld::kCtime);
+    io.custom_J = b->su.n_custom > 0 ? b->dev<double>(fld::kCustom) : nullptr;
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.fstar = b->dev<double>(fld::kFstar);
+    io.tau = b->dev<double>(fld::kTau);
+    io.wrench = b->dev<double>(fld::kWrench);
     io.wrench_ld = 6 * b->max_active;
-    io.status = b->d_status;
-    io.diag = b->d_diag;
+    io.status = b->dev<int>(fld::kStatus);
+    io.diag = b->dev<int>(fld::kDiag);
     io.dump = b->dump_on ? b->d_dump : nullptr;  // (never on an fp32 batch: the planner refuses it)
     io.body = f32 ? reinterpret_cast<const double *>(b->f_body) : b->d_body;  // real_t of the build that p.row belongs to
     io.topo = b->d_topo;
@@ -701,10 +688,11 @@ int dwbc_batch_solve(dwbc_batch *b, unsigned flags) {
 // ---- CalcContactRedistribute(torque_input, hqp, init) on a caller-supplied torque: the lean kernel of dwbc_redistribute.h
 int dwbc_batch_set_torque_input(dwbc_batch *b, const double *tau) {
     if (!tau) return fail("torque input is NULL");
-    if (b->d_tau_in && !b->own_tau_in) return fail("the torque input is bound to a device buffer");
+    Buf &u = b->buf[fld::kTauIn];
+    if (u.bound()) return fail("the torque input is bound to a device buffer");
     wait_uploads(b);
-    if (tau != b->h_tau_in.data()) memcpy(b->h_tau_in.data(), tau, b->h_tau_in.size() * sizeof(double));  // (dwbc_batch_host_ptr: already in place)
-    b->dirty_tau_in = true;
+    if (tau != u.h.as<double>()) memcpy(u.h.data(), tau, u.h.size());  // (dwbc_batch_host_ptr: already in place)
+    u.dirty = true;
     b->tau_in_set = true;
     return 1;
 }
@@ -726,14 +714,14 @@ static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
     }
     BatchIO io{};  // what stage 0 and the contact stage read; no output of the cycle is named
     io.B = b->B;
-    io.q = b->d_q;
-    io.flags = b->d_flags;
-    io.fstar = b->d_fstar;
+    io.q = b->dev<double>(fld::kQ);
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.fstar = b->dev<double>(fld::kFstar);
     io.body = b->d_body;
     io.topo = b->d_topo;
     io.hqp = 1;
     io.pair_swap_bit = -1;
-    RedistIO rio{b->d_tau_in, b->d_rd_tau, b->d_rd_cf, b->d_rd_wrench, b->d_rd_status};
+    RedistIO rio{b->dev<double>(fld::kTauIn), b->dev<double>(fld::kRdTau), b->dev<double>(fld::kRdCf), b->dev<double>(fld::kRdWrench), b->dev<int>(fld::kRdStatus)};
     void *args[] = {(void *)&b->su, (void *)&io, (void *)&rio};
     HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
     return 1;
@@ -749,19 +737,11 @@ static int redistribute_once(dwbc_batch *b, unsigned flags, dwbc_plan::Plan *pla
     if (!b->tau_in_set) return fail("no torque input: call dwbc_batch_set_torque_input (or bind DWBC_IN_TORQUE) first");
     HIP_OK(hipSetDevice(b->device));
     if (!upload_inputs(b)) return 0;
-    const size_t B = b->B, m = b->m;
-    if (!b->d_tau_in) { HIP_OK(hipMalloc(&b->d_tau_in, B * m * sizeof(double))); b->own_tau_in = true; b->dirty_tau_in = true; }
-    if (b->dirty_tau_in && b->own_tau_in) {
-        HIP_OK(hipMemcpyAsync(b->d_tau_in, b->h_tau_in.data(), b->h_tau_in.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        if (!b->ev_upload) HIP_OK(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(b->ev_upload, b->stream));
-        b->upload_pending = true;
-    }
-    b->dirty_tau_in = false;
-    if (!b->d_rd_tau) { HIP_OK(hipMalloc(&b->d_rd_tau, B * m * sizeof(double))); b->own_rd_tau = true; }
-    if (!b->d_rd_cf) { HIP_OK(hipMalloc(&b->d_rd_cf, B * 6 * sizeof(double))); b->own_rd_cf = true; }
-    if (!b->d_rd_wrench) { HIP_OK(hipMalloc(&b->d_rd_wrench, B * 24 * sizeof(double))); b->own_rd_wrench = true; }
-    if (!b->d_rd_status) { HIP_OK(hipMalloc(&b->d_rd_status, B * sizeof(int))); b->own_rd_status = true; }
+    bool queued = false;
+    if (!send(b, fld::kTauIn, &queued)) return 0;
+    if (queued && !mark_upload(b)) return 0;
+    for (const int f : {DWBC_REDIST_TAU, DWBC_REDIST_CF, DWBC_REDIST_WRENCH, DWBC_REDIST_STATUS})
+        if (!ensure_field(b, f)) return 0;
     if (planned) *planned = p;
     return launch_redistribute(b, p);
 }
@@ -809,47 +789,39 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     HIP_OK(hipSetDevice(dst->device));
     wait_uploads(dst);  // the target's mirrors are rewritten below
     dst->su = src->su;
-    auto clone = [&](double *&dd, bool &own, const double *sd, size_t count, PinnedVec<double> &hd, const PinnedVec<double> &hs, bool &dirty,
-                     bool src_own) -> int {
-        hd = hs;
-        if (count == 0) return 1;
-        if (!src_own || hs.size() != count) {  // the source reads a caller-owned device buffer: device-to-device copy
-            if (!own || !dd) { HIP_OK(hipMalloc(&dd, count * sizeof(double))); own = true; }
-            HIP_OK(hipMemcpy(dd, sd, count * sizeof(double), hipMemcpyDeviceToDevice));
-            hd.assign(count, 0.0);
-            HIP_OK(hipMemcpy(hd.data(), sd, count * sizeof(double), hipMemcpyDeviceToHost));
-            dirty = false;
-        } else {
-            dirty = true;
-        }
-        return 1;
-    };
-    if (!clone(dst->d_q, dst->own_q, src->d_q, (size_t)src->B * (src->n + 1), dst->h_q, src->h_q, dst->dirty_q, src->own_q)) return 0;
-    // f* and flags: (re)allocated by upload_inputs when the layout changed
-    dst->h_fstar = src->h_fstar;
-    dst->h_flags = src->h_flags;
-    if (dst->own_fstar && dst->d_fstar) { hipFree(dst->d_fstar); dst->d_fstar = nullptr; }
-    if (dst->own_flags && dst->d_flags) { hipFree(dst->d_flags); dst->d_flags = nullptr; }
-    dst->own_fstar = dst->own_flags = true;
-    dst->fstar_alloc = dst->flags_alloc = 0;
-    dst->dirty_fstar = dst->dirty_flags = true;
-    if (!src->own_fstar && src->d_fstar && src->su.fstar_total > 0) {
-        dst->h_fstar.assign((size_t)src->B * src->su.fstar_total, 0.0);
-        HIP_OK(hipMemcpy(dst->h_fstar.data(), src->d_fstar, dst->h_fstar.size() * sizeof(double), hipMemcpyDeviceToHost));
+    Buf &dq = dst->buf[fld::kQ];
+    const Buf &sq = src->buf[fld::kQ];
+    const size_t q_bytes = dwbc_batch_field_bytes(src, DWBC_IN_Q);
+    dq.h = sq.h;
+    dq.dirty = true;
+    if (sq.bound() || sq.h.size() != q_bytes) {  // the source reads a caller-owned device buffer: device-to-device copy
+        if (dq.bound()) release(dq);
+        if (!ensure(dq, q_bytes)) return 0;
+        HIP_OK(hipMemcpy(dq.d, sq.d, q_bytes, hipMemcpyDeviceToDevice));
+        dq.h.assign(q_bytes);
+        HIP_OK(hipMemcpy(dq.h.data(), sq.d, q_bytes, hipMemcpyDeviceToHost));
+        dq.dirty = false;
     }
-    if (!src->own_flags && src->d_flags && src->su.n_contacts > 0) {
-        dst->h_flags.assign((size_t)src->B * src->su.n_contacts, 0);
-        HIP_OK(hipMemcpy(dst->h_flags.data(), src->d_flags, dst->h_flags.size(), hipMemcpyDeviceToHost));
+    // f* and flags: the target's own buffers, (re)allocated by upload_inputs; what a bound source holds is read back from its device buffer
+    for (const int f : {DWBC_IN_FSTAR, DWBC_IN_CONTACT}) {
+        const int slot = fld::find(f)->idx;
+        Buf &d = dst->buf[slot];
+        const Buf &sb = src->buf[slot];
+        const size_t bytes = dwbc_batch_field_bytes(src, f);
+        release(d);
+        d.h = sb.h; d.dirty = true;
+        if (sb.bound() && bytes > 0) {
+            d.h.assign(bytes);
+            HIP_OK(hipMemcpy(d.h.data(), sb.d, bytes, hipMemcpyDeviceToHost));
+        }
     }
     // the contact capacity travels with the flags (a three-contact source would otherwise hand the two-contact product kernels rows
     // with three flags raised: status 0 on every such instance); after the flags, so that lowering is checked against the copied ones
     if (dst->max_active != src->max_active && !dwbc_batch_set_max_active_contacts(dst, src->max_active)) return 0;
-    dst->h_qdot = src->h_qdot; dst->dirty_qdot = !src->h_qdot.empty();
-    dst->h_ctime = src->h_ctime; dst->dirty_ctime = !src->h_ctime.empty();
-    dst->h_traj = src->h_traj; dst->dirty_traj = !src->h_traj.empty();
-    if (dst->d_traj) { hipFree(dst->d_traj); dst->d_traj = nullptr; }
-    dst->h_custom = src->h_custom; dst->dirty_custom = !src->h_custom.empty();
-    if (dst->d_custom) { hipFree(dst->d_custom); dst->d_custom = nullptr; }
+    for (const int slot : {fld::kQdot, fld::kCtime, fld::kTraj, fld::kCustom}) {  // (send() sizes the device buffer by the mirror)
+        dst->buf[slot].h = src->buf[slot].h;
+        dst->buf[slot].dirty = !src->buf[slot].h.empty();
+    }
     return 1;
 }
 
@@ -876,135 +848,36 @@ int dwbc_batch_time_solves(dwbc_batch *b, unsigned flags, int steps, float *ms) 
     return 1;
 }
 
-size_t dwbc_batch_field_bytes(const dwbc_batch *b, int field) {
-    const size_t B = b->B, n = b->n, m = b->m;
-    switch (field) {
-        case DWBC_IN_Q: return B * (n + 1) * 8;
-        case DWBC_IN_CONTACT: return B * b->su.n_contacts;
-        case DWBC_IN_FSTAR: return B * b->su.fstar_total * 8;
-        case DWBC_TAU: return B * 3 * m * 8;
-        case DWBC_WRENCH: return B * 6 * b->max_active * 8;
-        case DWBC_STATUS: return B * 4;
-        case DWBC_DIAG: return B * DG_COUNT * 4;
-        case DWBC_IN_TORQUE: case DWBC_REDIST_TAU: return B * m * 8;
-        case DWBC_REDIST_CF: return B * 6 * 8;
-        case DWBC_REDIST_WRENCH: return B * 24 * 8;
-        case DWBC_REDIST_STATUS: return B * 4;
-        case DWBC_TAU_GRAV: case DWBC_TAU_TASK: case DWBC_TAU_CONTACT: case DWBC_TAU_TOTAL: return B * m * 8;
-        case DWBC_A: case DWBC_A_INV: case DWBC_A_INV_N_C: return B * n * n * 8;
-        case DWBC_J_C: case DWBC_J_C_INV_T: return B * 12 * n * 8;
-        case DWBC_LAMBDA_C: return B * 144 * 8;
-        case DWBC_W_INV: return B * m * m * 8;
-        case DWBC_NWJW: return B * m * 6 * 8;
-        case DWBC_G: return B * n * 8;
-        case DWBC_P_C: return B * 12 * 8;
-        case DWBC_LINK_R: return B * kMaxBodies * 9 * 8;
-        case DWBC_LINK_P: return B * kMaxBodies * 3 * 8;
-        case DWBC_FSTAR_QP: case DWBC_CONTACT_QP: return B * kMaxLevels * 6 * 8;
-        case DWBC_CF_REDIS: return B * 6 * 8;
-        case DWBC_J_TASK: return B * kMaxLevels * 6 * n * 8;
-        case DWBC_LAMBDA_TASK: return B * kMaxLevels * 36 * 8;
-        case DWBC_J_KT: return B * kMaxLevels * m * 6 * 8;
-        case DWBC_QP_VIOL: return B * (kMaxLevels + 1) * 8;
-        case DWBC_DUMP_RAW: return B * (size_t)b->dl.total * 8;
-        case DWBC_CMM: case DWBC_J_COM: return B * 6 * n * 8;
-        case DWBC_COM: return B * 3 * 8;
-        case DWBC_COM_INERTIA: return B * 9 * 8;
-        case DWBC_B: return B * n * 8;
-        case DWBC_CONTACT_POS: return B * kMaxActiveContacts * 3 * 8;
-        case DWBC_CONTACT_ROT: return B * kMaxActiveContacts * 9 * 8;
-        case DWBC_ZMP: return B * (3 + kMaxActiveContacts * 3) * 8;
-        case DWBC_LINK_V: case DWBC_LINK_W: return B * kMaxBodies * 3 * 8;
-        case DWBC_A_R: case DWBC_A_R_INV: return B * kMaxReducedDof * kMaxReducedDof * 8;
-        case DWBC_G_R: return B * kMaxReducedDof * 8;
-        case DWBC_J_I_NC: case DWBC_J_I_NC_INV_T: return B * 6 * (n - 12) * 8;
-        default: return 0;
-    }
-}
-
 int dwbc_batch_get(dwbc_batch *b, int field, void *out, size_t bytes) {
+    const fld::Row *r = fld::find(field);
     const size_t need = dwbc_batch_field_bytes(b, field);
     if (need == 0) return fail("unknown field");
     if (bytes < need) return fail("output buffer too small");
     HIP_OK(hipSetDevice(b->device));
     HIP_OK(hipStreamSynchronize(b->stream));
-    const size_t B = b->B, m = b->m;
     // device -> page-locked staging (asynchronous on the batch's stream, PCIe rate) -> the caller's memory
     auto d2h = [&](const void *src, size_t nbytes) -> int {
-        if (b->h_stage.size() < nbytes) b->h_stage.resize(nbytes);
+        if (b->h_stage.size() < nbytes) b->h_stage.assign(nbytes);
         HIP_OK(hipMemcpyAsync(b->h_stage.data(), src, nbytes, hipMemcpyDeviceToHost, b->stream));
         HIP_OK(hipStreamSynchronize(b->stream));
         memcpy(out, b->h_stage.data(), nbytes);
         return 1;
     };
-    switch (field) {
-        case DWBC_IN_Q: return d2h(b->d_q, need);
-        case DWBC_IN_CONTACT: return d2h(b->d_flags, need);
-        case DWBC_IN_FSTAR: return d2h(b->d_fstar, need);
-        case DWBC_TAU: return d2h(b->d_tau, need);
-        case DWBC_WRENCH: return d2h(b->d_wrench, need);
-        case DWBC_STATUS: return d2h(b->d_status, need);
-        case DWBC_DIAG: return d2h(b->d_diag, need);
-        case DWBC_IN_TORQUE: return b->d_tau_in ? d2h(b->d_tau_in, need) : fail("no torque input on the device yet");
-        case DWBC_REDIST_TAU: case DWBC_REDIST_CF: case DWBC_REDIST_WRENCH: case DWBC_REDIST_STATUS: {
-            const void *src = field == DWBC_REDIST_TAU ? (const void *)b->d_rd_tau : field == DWBC_REDIST_CF ? (const void *)b->d_rd_cf
-                              : field == DWBC_REDIST_WRENCH ? (const void *)b->d_rd_wrench : (const void *)b->d_rd_status;
-            return src ? d2h(src, need) : fail("no redistribution output yet: call dwbc_batch_redistribute first");
-        }
-        case DWBC_TAU_GRAV: case DWBC_TAU_TASK: case DWBC_TAU_CONTACT: case DWBC_TAU_TOTAL: {
-            // one third of the bytes over PCIe: the part (or the sum, getTorqueCommand-style) is formed on the device
-            if (!b->d_total) HIP_OK(hipMalloc(&b->d_total, B * m * sizeof(double)));
-            const int sel = field == DWBC_TAU_GRAV ? 0 : field == DWBC_TAU_TASK ? 1 : field == DWBC_TAU_CONTACT ? 2 : 3;
-            const size_t cnt = B * m;
-            hipLaunchKernelGGL(dwbc_tau_select, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, b->stream, (const double *)b->d_tau, b->d_total, (int)m, cnt, sel);
-            HIP_OK(hipGetLastError());
-            return d2h(b->d_total, need);
-        }
-        default: break;
+    if (r->where == fld::kInSlot) {
+        const void *src = b->buf[r->idx].d;
+        return src || !r->absent ? d2h(src, need) : fail(r->absent);
+    }
+    if (r->where == fld::kTauPart) {
+        // one third of the bytes over PCIe: the part (or the sum, getTorqueCommand-style) is formed on the device
+        const size_t cnt = need / sizeof(double);
+        if (!b->d_total) HIP_OK(hipMalloc(&b->d_total, need));
+        hipLaunchKernelGGL(dwbc_tau_select, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, b->stream, (const double *)b->dev<double>(fld::kTau), b->d_total, b->m, cnt, r->idx);
+        HIP_OK(hipGetLastError());
+        return d2h(b->d_total, need);
     }
     if (!b->d_dump || !b->dump_on) return fail("intermediates need dwbc_batch_enable_dump(b, 1) before the solve");
-    const DumpLayout &dl = b->dl;
-    int off = 0, len = 0;
-    const int n = b->n, K = 6, T = kMaxTaskDof, L = kMaxLevels;
-    switch (field) {
-        case DWBC_A: off = dl.A; len = n * n; break;
-        case DWBC_A_INV: off = dl.A_inv; len = n * n; break;
-        case DWBC_J_C: off = dl.J_C; len = 12 * n; break;
-        case DWBC_LAMBDA_C: off = dl.Lambda_c; len = 144; break;
-        case DWBC_J_C_INV_T: off = dl.J_C_INV_T; len = 12 * n; break;
-        case DWBC_A_INV_N_C: off = dl.A_inv_N_C; len = n * n; break;
-        case DWBC_W_INV: off = dl.W_inv; len = (int)(m * m); break;
-        case DWBC_NWJW: off = dl.NwJw; len = (int)m * K; break;
-        case DWBC_G: off = dl.G; len = n; break;
-        case DWBC_CMM: off = dl.CMM; len = 6 * n; break;
-        case DWBC_J_COM: off = dl.J_com; len = 6 * n; break;
-        case DWBC_COM: off = dl.com; len = 3; break;
-        case DWBC_COM_INERTIA: off = dl.com_inertia; len = 9; break;
-        case DWBC_B: off = dl.B; len = n; break;
-        case DWBC_CONTACT_POS: off = dl.contact_pos; len = kMaxActiveContacts * 3; break;
-        case DWBC_CONTACT_ROT: off = dl.contact_rot; len = kMaxActiveContacts * 9; break;
-        case DWBC_ZMP: off = dl.zmp; len = 3 + kMaxActiveContacts * 3; break;
-        case DWBC_LINK_V: off = dl.link_v; len = kMaxBodies * 3; break;
-        case DWBC_LINK_W: off = dl.link_w; len = kMaxBodies * 3; break;
-        case DWBC_P_C: off = dl.P_C; len = 12; break;
-        case DWBC_LINK_R: off = dl.link_R; len = kMaxBodies * 9; break;
-        case DWBC_LINK_P: off = dl.link_p; len = kMaxBodies * 3; break;
-        case DWBC_FSTAR_QP: off = dl.fstar_qp; len = L * T; break;
-        case DWBC_CONTACT_QP: off = dl.contact_qp; len = L * K; break;
-        case DWBC_CF_REDIS: off = dl.cf_redis; len = K; break;
-        case DWBC_J_TASK: off = dl.J_task; len = L * T * n; break;
-        case DWBC_LAMBDA_TASK: off = dl.Lambda_task; len = L * T * T; break;
-        case DWBC_J_KT: off = dl.J_kt; len = L * (int)m * T; break;
-        case DWBC_QP_VIOL: off = dl.qp_viol; len = L + 1; break;
-        case DWBC_DUMP_RAW: off = 0; len = dl.total; break;
-        case DWBC_A_R: off = dl.A_R; len = kMaxReducedDof * kMaxReducedDof; break;
-        case DWBC_A_R_INV: off = dl.A_R_inv; len = kMaxReducedDof * kMaxReducedDof; break;
-        case DWBC_G_R: off = dl.G_R; len = kMaxReducedDof; break;
-        case DWBC_J_I_NC: off = dl.J_I_nc; len = 6 * (n - 12); break;
-        case DWBC_J_I_NC_INV_T: off = dl.J_I_nc_inv_T; len = 6 * (n - 12); break;
-        default: return fail("unknown field");
-    }
-    HIP_OK(hipMemcpy2D(out, (size_t)len * 8, b->d_dump + off, (size_t)dl.total * 8, (size_t)len * 8, B, hipMemcpyDeviceToHost));
+    const size_t row = need / b->B, off = r->off ? (size_t)(b->dl.*(r->off)) : 0;
+    HIP_OK(hipMemcpy2D(out, row, b->d_dump + off, (size_t)b->dl.total * sizeof(double), row, b->B, hipMemcpyDeviceToHost));
     return 1;
 }
 

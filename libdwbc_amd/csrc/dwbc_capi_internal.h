@@ -3,37 +3,63 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/dwbc_batch.h"
+#include "dwbc_fields.h"
 #include "dwbc_launch_plan.h"
 #include "dwbc_model.h"
 #include "dwbc_types.h"
 
 namespace dwbc {
-// host mirrors of the per-cycle inputs and the read-back staging live in page-locked memory: hipMemcpyAsync on the batch's stream
-// then really is asynchronous and runs at PCIe rate (pageable memory goes through the runtime's own staging, synchronously)
-template <class T>
-struct PinnedAlloc {
-    using value_type = T;
-    PinnedAlloc() = default;
-    template <class U>
-    PinnedAlloc(const PinnedAlloc<U> &) {}
-    T *allocate(size_t n) {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) throw std::bad_alloc();
-        return static_cast<T *>(p);
+// host memory of a batch: the mirrors of the per-cycle inputs and the read-back staging are page-locked, so that hipMemcpyAsync on the
+// batch's stream really is asynchronous and runs at PCIe rate (pageable memory goes through the runtime's own staging, synchronously:
+// that is what the rarely written task-reference inputs keep, and why nothing waits for their upload before they are rewritten)
+struct HostBytes {
+    bool pinned = true;  // set before the first allocation only
+    HostBytes() = default;
+    HostBytes(const HostBytes &) = delete;
+    HostBytes &operator=(const HostBytes &o) { return this != &o ? assign(o.p_, o.n_) : *this; }  // the contents; page-locked or not stays as it is here
+    ~HostBytes() { clear(); }
+    HostBytes &assign(const void *src, size_t n) {  // n bytes, a copy of src or (nullptr) zeros; the memory is kept while the size is
+        if (n != n_) {
+            if (p_) pinned ? (void)hipHostFree(p_) : free(p_);
+            p_ = nullptr;
+            n_ = 0;
+            if (n && pinned && hipHostMalloc((void **)&p_, n, hipHostMallocDefault) != hipSuccess) throw std::bad_alloc();
+            if (n && !pinned && !(p_ = (unsigned char *)malloc(n))) throw std::bad_alloc();
+            n_ = n;
+        }
+        if (n) src ? (void)memcpy(p_, src, n) : (void)memset(p_, 0, n);
+        return *this;
     }
-    void deallocate(T *p, size_t) { (void)hipHostFree(p); }
-    template <class U>
-    bool operator==(const PinnedAlloc<U> &) const { return true; }
-    template <class U>
-    bool operator!=(const PinnedAlloc<U> &) const { return false; }
+    void assign(size_t n) { assign(nullptr, n); }
+    void clear() { assign(nullptr, 0); }
+    bool empty() const { return n_ == 0; }
+    size_t size() const { return n_; }
+    unsigned char *data() const { return p_; }
+    template <class T>
+    T *as() const { return reinterpret_cast<T *>(p_); }
+    unsigned char operator[](size_t i) const { return p_[i]; }
+
+private:
+    unsigned char *p_ = nullptr;
+    size_t n_ = 0;
 };
-template <class T>
-using PinnedVec = std::vector<T, PinnedAlloc<T>>;
+// one device buffer of a batch (dwbc_fields::Slot): allocated by the batch or bound by the caller, with the host mirror it is uploaded
+// from where it has one
+struct Buf {
+    void *d = nullptr;
+    bool own = false;   // d was allocated by the batch (and is freed by it)
+    size_t bytes = 0;   // size of that allocation
+    HostBytes h;        // host mirror (empty: none, or not sized yet)
+    bool dirty = false; // the mirror is newer than the device buffer
+    bool bound() const { return d && !own; }
+};
 std::string &capi_err();  // thread-local last error (dwbc_last_error)
 inline int capi_fail(const std::string &s) {
     capi_err() = s;
@@ -55,21 +81,15 @@ struct dwbc_batch {
     int B = 0, device = 0, n = 0, m = 0;
     dwbc::Setup su{};
     hipStream_t stream = nullptr;
-    // device buffers (owned unless bound)
-    double *d_qdot = nullptr;  // B x n, allocated when the caller passes a qdot
-    double *d_traj = nullptr, *d_ctime = nullptr;  // on-device task reference inputs (dwbc_fstar.h)
-    double *d_custom = nullptr;  // B x n_custom x 6 x n: J_task of the TASK_CUSTOM levels
-    std::vector<double> h_custom;
-    bool dirty_custom = false;
-    std::vector<double> h_traj, h_ctime;
-    bool dirty_traj = false, dirty_ctime = false;
-    dwbc::PinnedVec<double> h_qdot;
-    bool dirty_qdot = false;
-    double *d_q = nullptr, *d_fstar = nullptr, *d_tau = nullptr, *d_wrench = nullptr, *d_dump = nullptr, *d_body = nullptr;
-    unsigned char *d_flags = nullptr;
-    int *d_status = nullptr, *d_diag = nullptr, *d_topo = nullptr;
-    bool own_q = false, own_fstar = false, own_flags = false, own_tau = false, own_wrench = false, own_status = false;
-    int fstar_alloc = 0, flags_alloc = 0;
+    // the device buffers that are owned or bound, with their host mirrors (dwbc_capi.hip: ensure / release / send); indexed by slot
+    dwbc::Buf buf[dwbc_fields::kSlotCount];
+    template <class T>
+    T *dev(int slot) const { return static_cast<T *>(buf[slot].d); }
+    dwbc_batch() {
+        for (int s : {dwbc_fields::kTraj, dwbc_fields::kCtime, dwbc_fields::kCustom}) buf[s].h.pinned = false;
+    }
+    double *d_dump = nullptr, *d_body = nullptr;
+    int *d_topo = nullptr;
     bool dump_on = false;
     int dtype = 0;  // DWBC_F64 | DWBC_F32 (arithmetic type of the kernels; the boundary buffers are always double)
     float *f_body = nullptr;
@@ -85,10 +105,7 @@ struct dwbc_batch {
     bool tree_match = false;  // tables[] holds a pack compiled for this model's parent table
     dwbc_plan::Plan last{};   // plan of the last accepted launch (row == nullptr: none yet): kernel_name / launch_info report it
     std::vector<const void *> lds_attr_set;  // kernels whose dynamic-LDS attribute has been raised on this batch's device
-    // host mirrors of the inputs
-    dwbc::PinnedVec<double> h_q, h_fstar;
-    dwbc::PinnedVec<unsigned char> h_flags;
-    dwbc::PinnedVec<unsigned char> h_stage;  // read-back staging of dwbc_batch_get
+    dwbc::HostBytes h_stage;  // read-back staging of dwbc_batch_get
     double *d_total = nullptr;                // B x m scratch of the DWBC_TAU_* getters
     double *d_jacc[dwbc::kMaxLevels] = {nullptr, nullptr, nullptr, nullptr};  // per task level: B x jacc_rec_size (dwbc_batch_solve_jacc)
     int *d_jacc_status = nullptr;             // kMaxLevels x B
@@ -97,18 +114,12 @@ struct dwbc_batch {
     int rrec_n = 0;
     double *d_jacc_nc = nullptr;              // B x jacc_nc_rec_size (dwbc_batch_solve_jacc_r_nc)
     int *d_jacc_nc_status = nullptr;
-    bool dirty_q = false, dirty_fstar = false, dirty_flags = false;
     // the mirrors are page-locked, so an upload returns before the DMA engine has read them: this event is recorded behind the
     // host-to-device copies of a solve and waited for before anything rewrites a mirror (dwbc_batch_set_*, dwbc_batch_host_ptr)
     hipEvent_t ev_upload = nullptr;
     bool upload_pending = false;
     int n_cu = 0;  // compute units of the batch's device
-    // dwbc_batch_redistribute: torque input (B x m; the mirror is created with the batch) and the outputs, allocated at the first launch
-    double *d_tau_in = nullptr, *d_rd_tau = nullptr, *d_rd_cf = nullptr, *d_rd_wrench = nullptr;
-    int *d_rd_status = nullptr;
-    bool own_tau_in = false, own_rd_tau = false, own_rd_cf = false, own_rd_wrench = false, own_rd_status = false;
-    dwbc::PinnedVec<double> h_tau_in;
-    bool dirty_tau_in = false, tau_in_set = false;
+    bool tau_in_set = false;  // dwbc_batch_redistribute has a torque input: set through the mirror (created with the batch) or bound
     dwbc::DumpLayout dl{};
 };
 

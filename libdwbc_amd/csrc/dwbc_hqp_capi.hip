@@ -395,14 +395,15 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
     // the dump record holds J_task at a stride of kMaxTaskDof rows per level (dwbc_hqp.h): a wider level, or a batch the
     // general-contact kernel solves (max_active > 2), has no record these configurators can read
     if (setup_wide_tasks(b->su) || b->max_active > 2) return fail("LQP / JACC: task levels of at most 6 dof");
-    if (b->h_flags.empty() || (b->d_flags && !b->own_flags)) return fail("LQP / JACC: contact flags must be set through dwbc_batch_set_contact (the host checks that they are uniform)");
+    const dwbc::Buf &uf = b->buf[dwbc_fields::kFlags];
+    if (uf.h.empty() || uf.bound()) return fail("LQP / JACC: contact flags must be set through dwbc_batch_set_contact (the host checks that they are uniform)");
     const int ncn = b->su.n_contacts;
     cfg = LqpCfg{};
     cfg.n = b->n;
     cfg.nc = 0;
     unsigned long long comask = 0x3full;
     for (int c = 0; c < ncn; c++)
-        if (b->h_flags[c]) {
+        if (uf.h[c]) {
             if (cfg.nc >= kMaxActiveContacts) return fail("LQP / JACC: more than 2 active contacts");
             cfg.act[cfg.nc] = c;
             cfg.lx[cfg.nc] = b->su.c_lx[c]; cfg.ly[cfg.nc] = b->su.c_ly[c]; cfg.mu[cfg.nc] = b->su.c_mu[c]; cfg.muz[cfg.nc] = b->su.c_muz[c];
@@ -410,7 +411,7 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
             cfg.nc++;
         }
     for (int i = 1; i < b->B; i++)
-        if (memcmp(&b->h_flags[(size_t)i * ncn], &b->h_flags[0], ncn) != 0)
+        if (memcmp(uf.h.data() + (size_t)i * ncn, uf.h.data(), ncn) != 0)
             return fail("LQP / JACC: every instance of the batch must be in the same contact state (the level sizes depend on it)");
     if (cfg.nc < 1) return fail("LQP / JACC: no active contact");
     cfg.cd = 6 * cfg.nc;
@@ -423,7 +424,7 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
     if (!reduced) {
         cfg.n_tasks = b->su.n_levels;
         for (int i = 0; i < b->su.n_levels; i++) { cfg.t_dof[i] = b->su.t_dof[i]; cfg.fstar_off[i] = b->su.fstar_off[i]; }
-        cfg.oBn = b->d_qdot ? b->dl.B : b->dl.G;  // B_(q, qdot = 0) = G_
+        cfg.oBn = b->buf[dwbc_fields::kQdot].d ? b->dl.B : b->dl.G;  // B_(q, qdot = 0) = G_
         cfg.jacc_mt = b->n - 6;
         return 1;
     }
@@ -503,17 +504,17 @@ static int configure_lqp_common(dwbc_batch *b, dwbc_hqp *h, bool reduced) {
     h->stream = b->stream;
     HIP_OK(hipSetDevice(b->device));
     hipLaunchKernelGGL(dwbc_lqp_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, cfg, h->d, hqp_io(h), (const double *)(reduced ? b->d_rrec : b->d_dump),
-                       (const double *)b->d_fstar);
+                       b->dev<const double>(dwbc_fields::kFstar));
     HIP_OK(hipGetLastError());
     return 1;
 }
 
 int dwbc_batch_reduced_dims(dwbc_batch *b, int *vc_dof, int *nc_dof) {
     if (!b || !vc_dof || !nc_dof) return fail("NULL argument");
-    if (b->h_flags.empty()) return fail("reduced dims: set the contact flags first");
+    if (b->buf[dwbc_fields::kFlags].h.empty()) return fail("reduced dims: set the contact flags first");
     unsigned long long comask = 0x3full;
     for (int c = 0; c < b->su.n_contacts; c++)
-        if (b->h_flags[c]) comask |= b->su.c_dofmask[c];
+        if (b->buf[dwbc_fields::kFlags].h[c]) comask |= b->su.c_dofmask[c];
     int vcd = 0;
     for (int j = 0; j < b->n; j++) vcd += (int)((comask >> j) & 1ull);
     if (comask != ((1ull << vcd) - 1ull) || (vcd != 12 && vcd != 18)) return fail("reduced dims: the contact chains must occupy the leading joint dofs");
@@ -582,10 +583,10 @@ static int solve_jacc_common(dwbc_batch *b, dwbc_hqp *h, int level, bool reduced
     JaccPrev prev{};
     for (int i = 0; i < level; i++) prev.rec[i] = b->d_jacc[i];
     const double *sys = reduced ? b->d_rrec : b->d_dump;
-    hipLaunchKernelGGL(dwbc_jacc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, cfg, level, prev, h->d, hqp_io(h), sys, (const double *)b->d_fstar);
+    hipLaunchKernelGGL(dwbc_jacc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, cfg, level, prev, h->d, hqp_io(h), sys, b->dev<const double>(dwbc_fields::kFstar));
     HIP_OK(hipGetLastError());
     if (!launch_solve(h, 0)) return 0;
-    hipLaunchKernelGGL(dwbc_jacc_extract_kernel, dim3(b->B), dim3(kNT), 0, b->stream, cfg, level, h->d, hqp_io(h), sys, (const double *)b->d_fstar,
+    hipLaunchKernelGGL(dwbc_jacc_extract_kernel, dim3(b->B), dim3(kNT), 0, b->stream, cfg, level, h->d, hqp_io(h), sys, b->dev<const double>(dwbc_fields::kFstar),
                        b->d_jacc[level], b->d_jacc_status + (size_t)level * b->B);
     HIP_OK(hipGetLastError());
     return 1;
@@ -629,7 +630,7 @@ int dwbc_batch_configure_lqp_r_nc(dwbc_batch *b, dwbc_hqp *h, const dwbc_hqp *hr
     h->stage.assign(h->d.n_levels, dwbc_hqp::Stage{});
     h->stream = b->stream;
     HIP_OK(hipSetDevice(b->device));
-    hipLaunchKernelGGL(dwbc_lqp_nc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, (const double *)b->d_fstar,
+    hipLaunchKernelGGL(dwbc_lqp_nc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, b->dev<const double>(dwbc_fields::kFstar),
                        (const double *)hr->d_rec);
     HIP_OK(hipGetLastError());
     return 1;
@@ -655,10 +656,10 @@ int dwbc_batch_solve_jacc_r_nc(dwbc_batch *b, dwbc_hqp *h, int level, int src_le
         HIP_OK(hipMemset(b->d_jacc_nc_status, 0, (size_t)b->B * sizeof(int)));
     }
     const double *prev = b->d_jacc[src_level];
-    hipLaunchKernelGGL(dwbc_jacc_nc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, (const double *)b->d_fstar, prev);
+    hipLaunchKernelGGL(dwbc_jacc_nc_configure_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, b->dev<const double>(dwbc_fields::kFstar), prev);
     HIP_OK(hipGetLastError());
     if (!launch_solve(h, 1)) return 0;
-    hipLaunchKernelGGL(dwbc_jacc_nc_extract_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, (const double *)b->d_fstar, prev,
+    hipLaunchKernelGGL(dwbc_jacc_nc_extract_kernel, dim3(b->B), dim3(kNT), 0, b->stream, c, h->d, hqp_io(h), (const double *)b->d_dump, b->dev<const double>(dwbc_fields::kFstar), prev,
                        b->d_jacc_nc, b->d_jacc_nc_status);
     HIP_OK(hipGetLastError());
     return 1;
@@ -669,7 +670,7 @@ int dwbc_batch_get_jacc_nc(dwbc_batch *b, int field, void *out, size_t bytes) {
     // nc_dof of the contact state the result was computed in
     unsigned long long comask = 0x3full;
     for (int c = 0; c < b->su.n_contacts; c++)
-        if (b->h_flags[c]) comask |= b->su.c_dofmask[c];
+        if (b->buf[dwbc_fields::kFlags].h[c]) comask |= b->su.c_dofmask[c];
     int vcd = 0;
     for (int j = 0; j < b->n; j++) vcd += (int)((comask >> j) & 1ull);
     const int ncd = b->n - vcd;

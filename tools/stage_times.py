@@ -35,10 +35,7 @@ for _ in range(3):
     wbc.solve()
 wbc.sync()
 print("kernel:", wbc.kernel_name())
-nb = wbc._L.dwbc_batch_field_bytes(wbc._h, 13)
-d = np.zeros(nb // 4, dtype=np.int32)
-wbc._L.dwbc_batch_get(wbc._h, 13, d.ctypes.data, nb)
-d = d.reshape(B, -1)
+d = wbc.get("diag")  # (the diagnostic build's record is longer than the product build's: the shape comes from the library)
 t = d[:, 74:90].astype(np.float64)
 # stamp index -> what has finished when it is taken (dwbc_cycle2.h / stage0 / stage1: DWBC_STAMP(i))
 names = {0: "kinematics + CRBA", 1: "A^-1 sweep", 2: "J_C, Lambda_c, Jbar, A^-1 N_c", 12: "NwJw, projector on null(W)", 13: "level-0 J_t, T1",

@@ -24,10 +24,7 @@ for _ in range(3):
     wbc.solve()
 wbc.sync()
 print("kernel:", wbc.kernel_name(), "flags", flags)
-nb = wbc._L.dwbc_batch_field_bytes(wbc._h, 13)  # the diag record is wider in the diagnostic build
-d = np.zeros(nb // 4, dtype=np.int32)
-wbc._L.dwbc_batch_get(wbc._h, 13, d.ctypes.data, nb)
-d = d.reshape(B, -1)
+d = wbc.get("diag")  # (the diagnostic build's record is longer than the product build's: the shape comes from the library)
 DG_TIME = 14 + 5 * 12
 names = ["kinematics + CRBA", "A^-1 (register sweep, 39)", "J_C, Y, Lambda_c (Gauss-Jordan 6 nc), Jbar", "A^-1 N_c", "Vb, NwJw, projector", "W^+ (register sweep, 33)",
          "FNl, gravity torque, P_C", "level 0: J_task, J_kt, chain", "level 0: QP inputs", "level 0: QP", "level 1: J_task, J_kt, chain", "level 1: QP inputs", "level 1: QP",

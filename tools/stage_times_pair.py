@@ -24,10 +24,7 @@ for _ in range(3):
     wbc.solve()
 wbc.sync()
 print("kernel:", wbc.kernel_name())
-nb = wbc._L.dwbc_batch_field_bytes(wbc._h, 13)
-d = np.zeros(nb // 4, dtype=np.int32)
-wbc._L.dwbc_batch_get(wbc._h, 13, d.ctypes.data, nb)
-d = d.reshape(B, -1)
+d = wbc.get("diag")  # (the diagnostic build's record is longer than the product build's: the shape comes from the library)
 t = np.median(d[:, 74:90].astype(np.float64), axis=0)      # DG_TIME: main arrivals 0..4, stamps 5.., 15
 f = np.median(d[:, 90:90 + 64].astype(np.float64), axis=0)  # DG_FTIME: helper arrivals 0..4, main departures 8..12
 names = ["B0 link frames", "B1 A^-1, riding rows | J_C, Vb, VG, Hb", "B2 Lambda_c, Jbar^T | D, Gram blocks", "B3 (gone)", "B4 W^+ a, T1 | Lambda_t, NwJw"]
