@@ -198,6 +198,23 @@ int dwbc_batch_set_control_time(dwbc_batch *b, const double *control_time);
 int dwbc_batch_set_torque_limit(dwbc_batch *b, const double *tau_lim);      /* SetTorqueLimit include/dwbc.h:249; NULL = unset */
 int dwbc_batch_fstar_size(const dwbc_batch *b);
 int dwbc_batch_task_dof(const dwbc_batch *b, int level);
+/* Per-instance torque limits and contact cone constants (no counterpart in the reference, where one RobotData is one robot): one record
+ * of dwbc_batch_instance_param_stride(b) = m + 4 * n_contacts doubles per instance,
+ *   [ tau_lim[0..m) | lx ly mu mu_z of registered contact 0 | ... of contact n_contacts - 1 ]      (registration order, not active order)
+ * While a batch has a record, instance i's QP rows -- the task QPs of dwbc_batch_solve and the QP of dwbc_batch_redistribute -- are
+ * filled from record i in place of dwbc_batch_set_torque_limit's values and the lx / ly / mu / mu_z of dwbc_batch_add_contact; the
+ * torque rows exist exactly as after dwbc_batch_set_torque_limit.  Contact points and links stay per batch.  It is no dwbc_field:
+ *   set   host is B x stride; every entry must be finite and > 0, otherwise 0 is returned and the batch keeps what it had.  Uploaded by
+ *         the next solve / redistribution on the batch's stream from a page-locked copy.  NULL drops the record: the batch-wide values
+ *         hold again.  Refused while a device buffer is bound.
+ *   bind  a caller-owned DEVICE buffer of B x stride doubles (a torch tensor), read in place by every later launch: no transfer and no
+ *         validation.  NULL unbinds (the batch-wide values hold again).
+ * dwbc_batch_add_contact and dwbc_batch_clear_contacts drop the record (the stride changes); dwbc_batch_copy_kinematics does not copy
+ * it.  Refused with a record (dwbc_last_error, nothing is launched): DWBC_SOLVE_REDUCED, DWBC_SOLVE_HQP clear (the closed form reads
+ * neither limits nor cones), dwbc_batch_configure_lqp* / dwbc_batch_solve_jacc* (one set of contact constants per batch). */
+int dwbc_batch_instance_param_stride(const dwbc_batch *b);
+int dwbc_batch_set_instance_params(dwbc_batch *b, const double *host);
+int dwbc_batch_bind_instance_params(dwbc_batch *b, void *device_ptr);
 
 /* UpdateKinematics(q, qdot, qddot) include/dwbc.h:251 : q is B x (ndof+1); qdot (B x ndof) may be NULL: only B_, the link
  * velocities and the on-device task reference read it; qddot is accepted for signature parity and unused */

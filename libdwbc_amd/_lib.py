@@ -102,6 +102,10 @@ SYMBOLS = [
     ("dwbc_batch_redistribute", _i, [_vp, C.c_uint]),
     ("dwbc_batch_time_redistribute", _i, [_vp, C.c_uint, _i, C.POINTER(C.c_float)]),
     ("dwbc_batch_redistribute_kernel_name", C.c_char_p, [_vp]),
+    # per-instance torque limits and contact cone constants
+    ("dwbc_batch_instance_param_stride", _i, [_vp]),
+    ("dwbc_batch_set_instance_params", _i, [_vp, _vp]),
+    ("dwbc_batch_bind_instance_params", _i, [_vp, _vp]),
 ]
 
 _lib = None

@@ -175,6 +175,8 @@ class Batch:
             raise DwbcError(_lib.last_error())
         self.n_contacts = 0
         self._keep = {}
+        self._contact_consts = []  # (lx, ly, mu, mu_z) per registered contact and the batch-wide torque limit: what a missing half of
+        self._tau_lim = None       # set_instance_params is filled from
 
     # ---- setup (shared by all instances)
     def add_contact(self, link, point, lx, ly, mu=0.2, mu_z=0.2, contact_type=CONTACT_6D):
@@ -183,6 +185,8 @@ class Batch:
         if i < 0:
             raise DwbcError(_lib.last_error())
         self.n_contacts = i + 1
+        self._contact_consts.append((float(lx), float(ly), float(mu), float(mu_z)))
+        self._keep.pop("instance_params", None)  # (the library dropped the record: its stride counts the contacts)
         return i
 
     def add_task(self, level, mode, link, point=(0.0, 0.0, 0.0)):
@@ -194,10 +198,58 @@ class Batch:
     def set_torque_limit(self, lim):
         if lim is None:
             _check(self._L.dwbc_batch_set_torque_limit(self._h, None))
+            self._tau_lim = None
         else:
             t = np.ascontiguousarray(lim, np.float64)
             assert t.shape == (self.m,)
             _check(self._L.dwbc_batch_set_torque_limit(self._h, t.ctypes.data))
+            self._tau_lim = t.copy()
+
+    # ---- per-instance torque limits and contact cone constants (domain randomisation: motor strength, friction, usable foot area)
+    @property
+    def instance_param_stride(self):
+        """doubles per instance of the parameter record: m + 4 * n_contacts"""
+        return int(self._L.dwbc_batch_instance_param_stride(self._h))
+
+    def set_instance_params(self, tau_lim=None, contact=None):
+        """Per-instance torque limits ``tau_lim`` (B, m) and contact constants ``contact`` (B, n_contacts, 4) = lx, ly, mu, mu_z in
+        registration order: they replace set_torque_limit's values and add_contact's constants in every QP row of solve() and
+        redistribute().  A missing half is filled from the batch-wide values (a missing ``tau_lim`` needs set_torque_limit first); both
+        None drops the record.  Every entry must be finite and > 0.  Refused with a record: solve(reduced=True), solve(hqp=False), LQP /
+        JACC.  add_contact drops the record."""
+        if tau_lim is None and contact is None:
+            _check(self._L.dwbc_batch_set_instance_params(self._h, None))
+            return
+        if self.n_contacts < 1:
+            raise DwbcError("instance parameters: add the contacts first")
+        rec = np.empty((self.B, self.instance_param_stride))
+        if tau_lim is None:
+            if self._tau_lim is None:
+                raise DwbcError("instance parameters: no tau_lim given and no batch-wide torque limit to fill it from (set_torque_limit)")
+            rec[:, : self.m] = self._tau_lim
+        else:
+            t = np.asarray(tau_lim, np.float64)
+            assert t.shape == (self.B, self.m), t.shape
+            rec[:, : self.m] = t
+        if contact is None:
+            rec[:, self.m :] = np.asarray(self._contact_consts, np.float64).reshape(-1)
+        else:
+            c = np.asarray(contact, np.float64)
+            assert c.shape == (self.B, self.n_contacts, 4), c.shape
+            rec[:, self.m :] = c.reshape(self.B, -1)
+        _check(self._L.dwbc_batch_set_instance_params(self._h, rec.ctypes.data))
+
+    def bind_instance_params(self, tensor):
+        """The record as a caller-owned device tensor of B x instance_param_stride float64, read in place by every later launch (no
+        transfer, no validation); None unbinds"""
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_instance_params(self._h, None))
+            self._keep.pop("instance_params", None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        assert tensor.numel() * tensor.element_size() == self.B * self.instance_param_stride * 8, tensor.shape
+        _check(self._L.dwbc_batch_bind_instance_params(self._h, C.c_void_p(tensor.data_ptr())))
+        self._keep["instance_params"] = tensor
 
     @property
     def fstar_size(self):
@@ -253,6 +305,8 @@ class Batch:
         """RobotData::CopyKinematicsData(target) (reference include/dwbc.h:375)"""
         _check(self._L.dwbc_batch_copy_kinematics(target._h, self._h))
         target.n_contacts = self.n_contacts
+        target._contact_consts = list(self._contact_consts)
+        target._tau_lim = None if self._tau_lim is None else self._tau_lim.copy()
 
     def set_max_active_contacts(self, n):
         """Contacts that may be active at once in one instance: 2 (default, the product kernels) or 3 -- every solve of the batch then

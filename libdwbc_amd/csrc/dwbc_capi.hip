@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -232,6 +233,7 @@ static dwbc_plan::Request plan_request(const dwbc_batch *b, bool reduced) {
     q.has_com_task = b->su.has_com_task != 0;
     q.n_custom = b->su.n_custom;
     q.dump_on = b->dump_on;
+    q.inst_par = b->buf[dwbc_fields::kInstPar].d || !b->buf[dwbc_fields::kInstPar].h.empty();
     q.no_wide = getenv("DWBC_NO_WIDE") != nullptr;
     q.no_pair = getenv("DWBC_NO_PAIR") != nullptr;
     q.no_lean = getenv("DWBC_NO_LEAN") != nullptr;
@@ -295,6 +297,18 @@ static int mark_upload(dwbc_batch *b) {
     HIP_OK(hipEventRecord(b->ev_upload, b->stream));
     b->upload_pending = true;
     return 1;
+}
+
+static void wait_uploads(dwbc_batch *b);
+// the per-instance parameter record, owned or bound, is let go of: the batch-wide values of the set-up hold again
+static void drop_instance_params(dwbc_batch *b) {
+    Buf &u = b->buf[fld::kInstPar];
+    if (!u.d && u.h.empty()) return;
+    hipSetDevice(b->device);
+    wait_uploads(b);
+    release(u);  // (hipFree waits for the launches that read it)
+    u.h.clear();
+    u.dirty = false;
 }
 
 dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype) {
@@ -380,6 +394,7 @@ int dwbc_batch_add_contact(dwbc_batch *b, int link, int contact_type, const doub
     std::string err;
     const int i = setup_add_contact(b->su, link, contact_type, point, lx, ly, mu, mu_z, err);
     if (i < 0) { fail(err); return -1; }
+    drop_instance_params(b);  // (its stride counts the contacts)
     b->buf[fld::kFlags].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_CONTACT));
     b->buf[fld::kFlags].dirty = true;
     return i;
@@ -387,6 +402,7 @@ int dwbc_batch_add_contact(dwbc_batch *b, int link, int contact_type, const doub
 
 int dwbc_batch_clear_contacts(dwbc_batch *b) {
     b->su.n_contacts = 0;
+    drop_instance_params(b);
     b->buf[fld::kFlags].h.clear();
     return 1;
 }
@@ -485,6 +501,30 @@ int dwbc_batch_set_torque_limit(dwbc_batch *b, const double *tau_lim) {
     if (!tau_lim) { b->su.has_tau_lim = 0; return 1; }
     b->su.has_tau_lim = 1;
     for (int i = 0; i < b->m; i++) b->su.tau_lim[i] = tau_lim[i];
+    return 1;
+}
+
+int dwbc_batch_instance_param_stride(const dwbc_batch *b) { return b->m + 4 * b->su.n_contacts; }
+
+int dwbc_batch_set_instance_params(dwbc_batch *b, const double *host) {
+    Buf &u = b->buf[fld::kInstPar];
+    if (u.bound()) return fail("the instance parameters are bound to a device buffer");
+    if (!host) { drop_instance_params(b); return 1; }
+    if (b->su.n_contacts < 1) return fail("instance parameters: register the contacts first (the record holds four constants per contact)");
+    const size_t cnt = (size_t)b->B * dwbc_batch_instance_param_stride(b);
+    for (size_t i = 0; i < cnt; i++)
+        if (!std::isfinite(host[i]) || !(host[i] > 0.0)) return fail("instance parameters: every torque limit and contact constant must be finite and > 0");
+    wait_uploads(b);
+    u.h.assign(host, cnt * sizeof(double));
+    u.dirty = true;
+    return 1;
+}
+
+int dwbc_batch_bind_instance_params(dwbc_batch *b, void *p) {
+    Buf &u = b->buf[fld::kInstPar];
+    if (!p && !u.bound()) return 1;  // nothing bound
+    drop_instance_params(b);
+    u.d = p;
     return 1;
 }
 
@@ -617,9 +657,17 @@ int dwbc_batch_enable_dump(dwbc_batch *b, int on) {
 
 static int upload_inputs(dwbc_batch *b) {
     bool queued = false;
-    for (const int slot : {fld::kTraj, fld::kCustom, fld::kCtime, fld::kQdot, fld::kQ, fld::kFlags, fld::kFstar})
+    for (const int slot : {fld::kTraj, fld::kCustom, fld::kCtime, fld::kInstPar, fld::kQdot, fld::kQ, fld::kFlags, fld::kFstar})
         if (!send(b, slot, &queued)) return 0;
     return queued ? mark_upload(b) : 1;
+}
+
+// the set-up a launch hands to the kernel: with a per-instance parameter record the torque rows exist as after dwbc_batch_set_torque_limit
+static const Setup *launch_setup(const dwbc_batch *b, const BatchIO &io, Setup &tmp) {
+    if (!io.inst_par || b->su.has_tau_lim) return &b->su;
+    tmp = b->su;
+    tmp.has_tau_lim = 1;
+    return &tmp;
 }
 
 // one launch of the cycle: the planner picks the build, whatever its arithmetic type or kind
@@ -659,7 +707,9 @@ static int launch(dwbc_batch *b, bool reduced) {
     io.hqp = b->hqp;
     io.pair_swap_bit = p.pair_swap_bit;
     io.warm = (b->warm && b->ws_valid) ? 1 : 0;
-    void *args[] = {(void *)&b->su, (void *)&io};
+    io.inst_par = b->dev<double>(fld::kInstPar);
+    Setup su_rec;
+    void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io};
     HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
     b->ws_valid = p.ws_valid_after;
     b->last = p;
@@ -721,8 +771,10 @@ static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
     io.topo = b->d_topo;
     io.hqp = 1;
     io.pair_swap_bit = -1;
+    io.inst_par = b->dev<double>(fld::kInstPar);
+    Setup su_rec;
     RedistIO rio{b->dev<double>(fld::kTauIn), b->dev<double>(fld::kRdTau), b->dev<double>(fld::kRdCf), b->dev<double>(fld::kRdWrench), b->dev<int>(fld::kRdStatus)};
-    void *args[] = {(void *)&b->su, (void *)&io, (void *)&rio};
+    void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io, (void *)&rio};
     HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
     return 1;
 }
@@ -788,6 +840,7 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     if (dst->B != src->B || dst->n != src->n || dst->su.nb != src->su.nb) return fail("CopyKinematicsData: batch size / model mismatch");
     HIP_OK(hipSetDevice(dst->device));
     wait_uploads(dst);  // the target's mirrors are rewritten below
+    if (dst->su.n_contacts != src->su.n_contacts) drop_instance_params(dst);  // (never copied; the target's own goes with its stride)
     dst->su = src->su;
     Buf &dq = dst->buf[fld::kQ];
     const Buf &sq = src->buf[fld::kQ];

@@ -421,16 +421,24 @@ struct QpLaneConst {
     PL(int, row2);
     PL(int, rowo);
 };
+// inst_par (BatchIO::inst_par) != nullptr: the instance's own record [tau_lim[M] | lx ly mu muz per registered contact] takes the place of
+// the batch-wide values of the set-up -- one wave-uniform branch, the same two loads per lane from another address
 template <int N>
-DWBC_DEV void qp_lane_consts(const Setup &su, int ci0, int ci1, QpLaneConst &qc) {
+DWBC_DEV void qp_lane_consts(const Setup &su, const io_t *inst_par, int inst, int ci0, int ci1, QpLaneConst &qc) {
     constexpr int M = N - 6;
     DWBC_LANE_DECL;
+    const io_t *rec = inst_par ? inst_par + (size_t)inst * (M + 4 * su.n_contacts) : nullptr;
     LANES {
-        LV(qc.taul) = lane < M ? (real_t)su.tau_lim[lane] : real_t(0.0);
         const int rr = lane >= M ? lane - M : 0, a = rr >= 10 ? 1 : 0, r10 = rr - 10 * a;
         const int ci = a ? ci1 : ci0;
         const int pr = r10 >> 1;
-        LV(qc.c2) = -(real_t)(pr == 0 ? su.c_lx[ci] : pr == 1 ? su.c_ly[ci] : pr == 4 ? su.c_muz[ci] : su.c_mu[ci]);
+        if (rec) {
+            LV(qc.taul) = lane < M ? (real_t)rec[lane] : real_t(0.0);
+            LV(qc.c2) = -(real_t)rec[M + 4 * ci + (pr == 0 ? 0 : pr == 1 ? 1 : pr == 4 ? 3 : 2)];
+        } else {
+            LV(qc.taul) = lane < M ? (real_t)su.tau_lim[lane] : real_t(0.0);
+            LV(qc.c2) = -(real_t)(pr == 0 ? su.c_lx[ci] : pr == 1 ? su.c_ly[ci] : pr == 4 ? su.c_muz[ci] : su.c_mu[ci]);
+        }
         const int oi = pr == 0 ? 4 : pr == 1 ? 3 : pr == 2 ? 0 : pr == 3 ? 1 : 5;
         LV(qc.sg) = (pr < 2) ? ((r10 & 1) ? real_t(1.0) : -real_t(1.0)) : ((r10 & 1) ? -real_t(1.0) : real_t(1.0));
         LV(qc.row2) = 6 * a + 2;
@@ -464,7 +472,7 @@ DWBC_DEV void qp_rows_and_solve(const Setup &su, real_t *L, int nlim, int ncone,
                                 int t1, const real_t *P2, int ld2, int t2, real_t s2, const real_t *W1, int ldw1,
                                 const real_t *W2, int ldw2, const real_t *fv, const real_t *base, int tvars, int max_iter,
                                 QpResult &res, real_t *Vlds, real_t *xlds, const int *warm, const QpLaneConst *qcp,
-                                real_t vtol, PL_REF(real_t, sfin)) {
+                                real_t vtol, PL_REF(real_t, sfin), const io_t *inst_par = nullptr, int inst = 0) {
     constexpr int M = N - 6;
     DWBC_LANE_DECL;
     QpRows R;
@@ -473,7 +481,7 @@ DWBC_DEV void qp_rows_and_solve(const Setup &su, real_t *L, int nlim, int ncone,
     const long long t_fill0_ = clock64();
 #endif
     QpLaneConst qloc;
-    if (!qcp) qp_lane_consts<N>(su, ci0, ci1, qloc);  // (callers that solve one QP only)
+    if (!qcp) qp_lane_consts<N>(su, inst_par, inst, ci0, ci1, qloc);  // (callers that solve one QP only)
     const QpLaneConst &qc = qcp ? *qcp : qloc;
     // One straight-line path for every lane: entry j of a row is  ca * A_j + cb * B_j  with A / B taken from the left block (j < t1) or the
     // right block, by UNCONDITIONAL loads (clamped addresses, the value masked afterwards) -- 24 independent LDS reads the scheduler can

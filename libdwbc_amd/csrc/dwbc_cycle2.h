@@ -1640,7 +1640,7 @@ DWBC_DEV void cycle_instance_v2(Thr th, const Setup &su, const BatchIO &io, int 
     bool skip_redis = false;
     const bool wm_ok = kExtras ? io.hqp != 0 : true;  // the wrench maps exist (hqp = true)
     if (wm_ok) {
-        qp_lane_consts<N>(su, act_c[0], act_c[1], qc);
+        qp_lane_consts<N>(su, io.inst_par, inst, act_c[0], act_c[1], qc);
         wrench_maps<N, NT, S>(th, su, L, JbT, cd, k, WM);
         // wacc = wrench of the torque committed so far (gravity torque to begin with) minus A_rot P_C, contact-local frames
         for (int i = th.tid; i < C; i += NT) {

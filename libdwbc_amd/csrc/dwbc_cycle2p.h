@@ -1131,7 +1131,7 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     PL(real_t, tta);   // what the committed levels add to it: sum_l gd_l . (f*_l + f*_qp_l)  (torque lanes: torque_task_[lane])
     PL(real_t, Tl);    // torque lanes: the torque limit; cone lanes: 0
     bool skip_redis = false;
-    qp_lane_consts<N>(su, act_c[0], act_c[1], qc);
+    qp_lane_consts<N>(su, io.inst_par, inst, act_c[0], act_c[1], qc);
     wrench_maps<N, NT, S>(th, su, L, JbT, cd, k, WM);
     DWBC_SYNC();
     LANES {

@@ -287,8 +287,9 @@ DWBC_DEVN real_t gj_inverse_rows(Thr th, const real_t *A, int lda, int n, real_t
 // QP rows into lanes + solve, for up to NCC contacts (same rows as qp_rows_and_solve of dwbc_cycle.h):
 //   torque rows:  [P1 | s2 P2][r,:] x  in  [-(lim + base), lim - base]        (reference src/dwbc.cpp:1001-1016)
 //   cone rows:    -cone(W1 | s2 W2)[rr,:] x <= cone(fv)[rr]                     (reference src/dwbc.cpp:1041-1053, src/wbd.cpp:59-97)
+// rec: the instance's record of BatchIO::inst_par (layout: qp_lane_consts of dwbc_cycle.h) or nullptr for the batch-wide values of su
 template <int N, int NCC, int TG = kMaxTaskDof>
-DWBC_DEV void qp_rows_and_solve_gc(const Setup &su, int nlim, int ncone, const int *act_c, const real_t *P1, int ld1, int t1,
+DWBC_DEV void qp_rows_and_solve_gc(const Setup &su, const io_t *rec, int nlim, int ncone, const int *act_c, const real_t *P1, int ld1, int t1,
                                    const real_t *P2, int ld2, int t2, real_t s2, const real_t *W1, int ldw1, const real_t *W2, int ldw2,
                                    const real_t *fv, const real_t *base, int tvars, int max_iter, QpResultT<TG + 6 * NCC - 6> &res,
                                    real_t *Vlds, real_t *xlds, real_t vtol, bool fixed_layout = false) {
@@ -320,8 +321,9 @@ DWBC_DEV void qp_rows_and_solve_gc(const Setup &su, int nlim, int ncone, const i
                     else if (j >= off2 && j < off2 + t2) v = P2[lane * ld2 + (j - off2)] * s2;
                     LV(R.g)[j] = v;
                 }
-                LV(R.hi) = (real_t)su.tau_lim[lane] - base[lane];
-                LV(R.lo) = (real_t)su.tau_lim[lane] + base[lane];
+                const real_t lim = rec ? (real_t)rec[lane] : (real_t)su.tau_lim[lane];
+                LV(R.hi) = lim - base[lane];
+                LV(R.lo) = lim + base[lane];
                 LV(R.id_hi) = lane;
                 LV(R.id_lo) = M + lane;
             }
@@ -330,7 +332,8 @@ DWBC_DEV void qp_rows_and_solve_gc(const Setup &su, int nlim, int ncone, const i
             const int rr = lane - M, a = rr / 10, r10 = rr - 10 * a;
             const int ci = act_c[a];
             const int pr = r10 >> 1;
-            const real_t c2 = -(real_t)(pr == 0 ? su.c_lx[ci] : pr == 1 ? su.c_ly[ci] : pr == 4 ? su.c_muz[ci] : su.c_mu[ci]);
+            const real_t c2 = rec ? -(real_t)rec[M + 4 * ci + (pr == 0 ? 0 : pr == 1 ? 1 : pr == 4 ? 3 : 2)]
+                                  : -(real_t)(pr == 0 ? su.c_lx[ci] : pr == 1 ? su.c_ly[ci] : pr == 4 ? su.c_muz[ci] : su.c_mu[ci]);
             const int oi = pr == 0 ? 4 : pr == 1 ? 3 : pr == 2 ? 0 : pr == 3 ? 1 : 5;
             const real_t sg = (pr < 2) ? ((r10 & 1) ? real_t(1.0) : -real_t(1.0)) : ((r10 & 1) ? -real_t(1.0) : real_t(1.0));
             const int row2 = 6 * a + 2, rowo = 6 * a + oi;
@@ -701,6 +704,7 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
     // ================= stage 3: task cascade (dwbc.cpp:685-873, 941-1127; wbd.cpp:207-261) =================
     const int nlim = su.has_tau_lim ? 2 * M : 0;
     const int ncone = 10 * nc;
+    const io_t *rec = io.inst_par ? io.inst_par + (size_t)inst * (M + 4 * su.n_contacts) : nullptr;
     int st_task = 1, fail_level = -1;
     const io_t *fs_in = io.fstar + (size_t)inst * su.fstar_total;
     if (su.has_com_task)  // out of Xl / Yl before the first level writes them (the contact scratch under t_Jcm is dead: stage 2 fenced)
@@ -821,7 +825,7 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
             DWBC_SYNC();
             if (lv < 2) DWBC_STAMP(8 + 3 * lv);  // level lv: QP inputs
             QpResultT<QN> qres;
-            qp_rows_and_solve_gc<N, NCC, TG>(su, nlim, ncone, act_c, U, T, t, L + S::NwJw, k, k, kQpScaleGI, F, T, L + S::FNl, k, fv, base, t,
+            qp_rows_and_solve_gc<N, NCC, TG>(su, rec, nlim, ncone, act_c, U, T, t, L + S::NwJw, k, k, kQpScaleGI, F, T, L + S::FNl, k, fv, base, t,
                                          su.qp_max_iter_task, qres, L + S::qp_V, L + S::qp_x, kQpTol, true);
             if (lv < 2) DWBC_STAMP(9 + 3 * lv);  // level lv: QP solved
             if (diag && th.tid == 0) {
@@ -867,7 +871,7 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
         DWBC_SYNC();
         QpResultT<QN> qres;
         // (canon rule 5: the redistribution QP searches with the feasibility tolerance the task QPs were accepted at)
-        qp_rows_and_solve_gc<N, NCC, TG>(su, nlim, ncone, act_c, L + S::NwJw, k, k, L + S::NwJw, k, 0, real_t(1.0), L + S::FNl, k, L + S::FNl, k, fv,
+        qp_rows_and_solve_gc<N, NCC, TG>(su, rec, nlim, ncone, act_c, L + S::NwJw, k, k, L + S::NwJw, k, 0, real_t(1.0), L + S::FNl, k, L + S::FNl, k, fv,
                                      base, k, su.qp_max_iter_contact, qres, L + S::qp_V, L + S::qp_x, kQpFeasTol);
         if (diag && th.tid == 0) {
             diag[DG_QP_ITER + kMaxLevels] = qres.iters;

@@ -12,8 +12,9 @@ namespace dwbc_fields {
 using namespace dwbc;
 
 // device buffers of a batch that are owned or bound, sized once and uploaded from a host mirror if they have one: the bindable fields,
-// the diagnostics record, and the inputs that are no field (dwbc_batch::buf is indexed by this)
-enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kSlotCount };
+// the diagnostics record, and the inputs that are no field -- the task-reference inputs and the per-instance parameter record
+// (dwbc_batch::buf is indexed by this)
+enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kInstPar, kSlotCount };
 
 // one extent of a shape: mul * var + add
 enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal };

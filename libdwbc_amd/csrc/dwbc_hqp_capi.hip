@@ -414,6 +414,8 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
         if (memcmp(uf.h.data() + (size_t)i * ncn, uf.h.data(), ncn) != 0)
             return fail("LQP / JACC: every instance of the batch must be in the same contact state (the level sizes depend on it)");
     if (cfg.nc < 1) return fail("LQP / JACC: no active contact");
+    if (b->buf[dwbc_fields::kInstPar].d || !b->buf[dwbc_fields::kInstPar].h.empty())
+        return fail("LQP / JACC: per-instance parameters are not built here (the formulation takes one set of contact constants for the batch): drop them with dwbc_batch_set_instance_params(b, NULL)");
     cfg.cd = 6 * cfg.nc;
     cfg.fstar_total = b->su.fstar_total;
     cfg.tlim = 200.0;  // `tlim`, src/dwbc.cpp:4360

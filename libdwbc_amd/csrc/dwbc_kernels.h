@@ -100,7 +100,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
 // dwbc_capi.hip fills one BatchIO for the kernels of both arithmetic types: the members that differ are pointers
-static_assert(sizeof(BatchIO) == 8 + 14 * sizeof(void *) + 4 * sizeof(int) && offsetof(BatchIO, body) == 8 + 12 * sizeof(void *),
+static_assert(sizeof(BatchIO) == 8 + 15 * sizeof(void *) + 4 * sizeof(int) && offsetof(BatchIO, body) == 8 + 12 * sizeof(void *),
               "BatchIO layouts of the two builds must match");
 
 // ---- the launch table (dwbc_launch_plan.h): one row per launchable kernel.  DWBC_ROW instantiates KERNEL<template arguments> and

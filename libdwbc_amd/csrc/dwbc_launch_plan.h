@@ -55,6 +55,9 @@ struct Request {
     // not a cycle: CalcContactRedistribute(torque_input, hqp, init) on a caller-supplied torque (dwbc_batch_redistribute); of the members
     // above it reads the model, arith, max_active and hqp
     bool redistribute = false;
+    // the batch carries per-instance torque limits and contact cone constants (BatchIO::inst_par): every kernel of the table reads them where
+    // it fills a QP row, so no route changes; what has no QP rows to put them in is refused
+    bool inst_par = false;
 };
 
 struct Plan {
@@ -143,13 +146,17 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
     // a tree without a lean build starts warm one solve later.)
     const bool ws_valid_after = q.arith == kFloat ? !lean_asked : (!lean && !q.reduced);
     // two waves per instance, side chains on the helper wave: the lean fp64 cycle of small batches (one instance per SIMD)
-    if ((wide || q.pair_always) && lean && !q.reduced && q.arith == kDouble && !q.no_pair)
-        if (const Row *r = c.pick(kTwoWave, kTwoWave)) {
-            p.pair_swap_bit = q.pair_swap_bit;
-            return run(r, ws_valid_after);
-        }
-    const Row *r = c.pick(kWide | kLean | kTwoWave, (wide ? kWide : 0u) | (lean ? kLean : 0u));
-    return r ? run(r, ws_valid_after) : refuse("no kernel for this model / number of task levels");
+    const Row *r = nullptr;
+    if ((wide || q.pair_always) && lean && !q.reduced && q.arith == kDouble && !q.no_pair) r = c.pick(kTwoWave, kTwoWave);
+    const bool two_wave = r != nullptr;
+    if (!r) r = c.pick(kWide | kLean | kTwoWave, (wide ? kWide : 0u) | (lean ? kLean : 0u));
+    if (!r) return refuse("no kernel for this model / number of task levels");
+    // per-instance parameters shape QP rows: the reduced path refuses a torque limit already, and the closed form of hqp = false knows neither
+    // limits nor cones (a randomisation that is silently ignored is worse than a refusal)
+    if (q.inst_par && q.reduced) return refuse("per-instance parameters: not built on the reduced dynamics path (drop them with dwbc_batch_set_instance_params(b, NULL))");
+    if (q.inst_par && !q.hqp) return refuse("per-instance parameters: hqp = true only (the closed form of hqp = false reads neither torque limits nor contact cones)");
+    if (two_wave) p.pair_swap_bit = q.pair_swap_bit;
+    return run(r, ws_valid_after);
 }
 
 }  // namespace dwbc_plan

@@ -247,7 +247,7 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
         PL(real_t, sfin);
         // x = c (k), H = I: rows [NwJw] against the torque limits, cone(WM[:, 1:]) against cone(fv); no second block
         qp_rows_and_solve<N, NB, 0>(su, L, nlim, ncone, act_c[0], act_c[1], L + S::NwJw, 6, k, L + S::NwJw, 6, 0, real_t(1.0), WM + 1, WLD, WM + 1, WLD,
-                                    fv, tin, k, su.qp_max_iter_contact, qres, L + S::qp_V, L + S::qp_x, nullptr, nullptr, kQpFeasTol, sfin);
+                                    fv, tin, k, su.qp_max_iter_contact, qres, L + S::qp_V, L + S::qp_x, nullptr, nullptr, kQpFeasTol, sfin, io.inst_par, inst);
         if (qres.status) {
 #pragma unroll
             for (int j = 0; j < 6; j++) xq[j] = j < k ? L[S::qp_x + j] : real_t(0.0);

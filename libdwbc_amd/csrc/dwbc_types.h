@@ -169,6 +169,8 @@ struct BatchIO {  // device pointers.  Inputs and outputs are io_t (double) in b
                                  // the rows of its previous working set (diag[DG_QP_ACT..], written by the previous launch)
     int wrench_ld;               // general-contact kernel (dwbc_cycle_gc.h): doubles per instance in `wrench` (18 for three contacts); the
                                  // product kernels write 12 per instance and do not read it
+    const io_t *inst_par;        // B x (M + 4 n_contacts) or nullptr: per instance [tau_lim[M] | lx ly mu muz of every registered contact], read
+                                 // in place of Setup::tau_lim / c_lx / c_ly / c_mu / c_muz where a QP row is filled (dwbc_cycle.h: qp_lane_consts)
 };
 
 }  // namespace dwbc
