@@ -2,16 +2,20 @@
 // one "thread" per workgroup (NT = 1, barriers are no-ops) so that the arithmetic and indexing of the fused
 // cycle can be checked against the oracle on a machine without a GPU (pytest -m "not gpu").  It shares the
 // product's URDF reader and Setup builder, which this also covers.  It is never linked into libdwbc_hip.so and
-// is not a fallback: the product has no CPU path.
+// is not a fallback: the product has no CPU path.  The only harness file: every cycle kernel (dwbc_cycle2.h, dwbc_cycle2p.h,
+// dwbc_reduced.h, dwbc_cycle_gc.h), the redistribution kernel (dwbc_redistribute.h) and the HQP class (dwbc_hqp.h) have their entry
+// points here, and a run is described by its arguments alone (EmuRun): nothing is left behind between two runs but the context.
 #define DWBC_HOST_EMU 1
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../libdwbc_amd/csrc/dwbc_reduced.h"
+#include "../../libdwbc_amd/csrc/dwbc_redistribute.h"
 #include "../../libdwbc_amd/csrc/dwbc_cycle2p.h"
 #include "../../libdwbc_amd/csrc/dwbc_cycle_gc.h"
 #include "../../libdwbc_amd/csrc/dwbc_hqp.h"
@@ -39,6 +43,90 @@ struct EmuCtx {
     std::vector<int> topo;
     std::string err;
 };
+
+// which instantiation of the cycle a run executes
+enum EmuBuild : int {
+    EMU_EXTRAS = 0,      // one-wave kernel with the extras (public matrices, dump record), TOCABI's constant tree
+    EMU_EXTRAS_GENERIC,  // the same on TopoGeneric
+    EMU_COMPACT,         // lean build on the compact LDS map (Lds3)
+    EMU_TWO_WAVE,        // paired kernel (dwbc_cycle2p.h), lean
+    EMU_REDUCED,         // the Reduced* call sequence (dwbc_reduced.h)
+    EMU_GC               // general-contact kernel (dwbc_cycle_gc.h)
+};
+// everything a run reads beyond the context: mirrored by the ctypes.Structure EmuRun of emu.py
+struct EmuRun {
+    EmuBuild build;
+    int hqp;   // BatchIO::hqp
+    int warm;  // BatchIO::warm: `diag` holds the working sets of a previous run on entry
+    const double *qdot, *traj, *ctime, *custom_J, *inst_par;  // optional, nullptr = absent (shapes: BatchIO)
+};
+
+// As the launcher does (dwbc_capi.hip: launch_setup), a run with a per-instance record hands the kernel a set-up whose torque rows exist.
+static Setup run_setup(const EmuCtx *c, const double *inst_par) {
+    Setup s = c->su;
+    if (inst_par) s.has_tau_lim = 1;
+    return s;
+}
+
+// BatchIO of a run with the real_t copies it points into: the body table and the staged dump record
+struct EmuIO {
+    BatchIO io{};
+    std::vector<real_t> body, dump;
+    double *dump_out;
+    EmuIO(const EmuCtx *c, const EmuRun &r, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau, double *wrench,
+          int *status, int *diag, double *dump_)
+        : body(to_real(c->body.data(), c->body.size())), dump(dump_ ? (size_t)B * DumpLayout::make(c->model.ndof).total : 0), dump_out(dump_) {
+        io.B = B;
+        io.q = q;
+        io.qdot = r.qdot;
+        io.flags = flags;
+        io.fstar = fstar;
+        io.traj = c->su.n_traj > 0 ? r.traj : nullptr;
+        io.ctime = r.ctime;
+        io.custom_J = c->su.n_custom > 0 ? r.custom_J : nullptr;
+        io.tau = tau;
+        io.wrench = wrench;
+        io.status = status;
+        io.diag = diag;
+        io.dump = dump_ ? dump.data() : nullptr;
+        io.body = body.data();
+        io.topo = c->topo.data();
+        io.hqp = r.hqp;
+        io.pair_swap_bit = -1;
+        io.warm = r.warm;
+        io.inst_par = r.inst_par;
+    }
+    void finish() { from_real(dump, dump_out); }
+};
+
+// the run-time level count 1 - 4 as a template argument: f(std::integral_constant<int, NLV>{})
+template <class F>
+static void with_levels(int n_levels, F &&f) {
+    switch (n_levels) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{});
+    }
+}
+template <template <int, int, int> class Map>
+static int lds_bytes(int n_levels) {
+    int bytes = 0;
+    with_levels(n_levels, [&](auto k) { bytes = Map<39, 34, decltype(k)::value>::total_bytes; });
+    return bytes;
+}
+
+// f(b, lds) for every instance of the batch on `reals` reals of LDS, poisoned with NaN before every instance of every build: a read of a
+// block that nothing has written yet shows up in the result
+static void poison(std::vector<real_t> &lds) { std::fill(lds.begin(), lds.end(), std::numeric_limits<real_t>::quiet_NaN()); }
+template <class F>
+static void each_instance(int B, size_t reals, F &&f) {
+    std::vector<real_t> lds(reals + 64);
+    for (int b = 0; b < B; b++) {
+        poison(lds);
+        f(b, lds.data());
+    }
+}
 
 extern "C" {
 
@@ -106,196 +194,110 @@ int emu_dump_offset(EmuCtx *c, const char *name) {
 }
 int emu_diag_count() { return DG_COUNT; }
 int emu_lds_bytes() { return Lds2<39, 34, 2>::total_bytes; }
-
-int emu_lds_bytes_reduced(int nlv) { return nlv == 1 ? LdsR<39, 34, 1>::total_bytes : nlv == 2 ? LdsR<39, 34, 2>::total_bytes : nlv == 3 ? LdsR<39, 34, 3>::total_bytes : LdsR<39, 34, 4>::total_bytes; }
-int emu_lds_bytes_v2(int nlv) { return nlv == 1 ? Lds2<39, 34, 1>::total_bytes : nlv == 2 ? Lds2<39, 34, 2>::total_bytes : nlv == 3 ? Lds2<39, 34, 3>::total_bytes : Lds2<39, 34, 4>::total_bytes; }
-
-int emu_run_reduced(EmuCtx *c, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau,
-                    double *wrench, int *status, int *diag, double *dump) {
-    if (c->model.ndof != 39 || c->model.nb != 34) { c->err = "emu is instantiated for TOCABI (39 dof) only"; return 0; }
-    const int n = 39, m = 33;
-    const size_t D = DumpLayout::make(n).total;
-    (void)m;
-    auto rb = to_real(c->body.data(), c->body.size());
-    std::vector<real_t> rdump(dump ? (size_t)B * D : 0);
-    BatchIO io{};
-    io.B = B; io.q = q; io.flags = flags; io.fstar = fstar; io.tau = tau; io.wrench = wrench; io.status = status;
-    io.diag = diag; io.dump = dump ? rdump.data() : nullptr; io.body = rb.data(); io.topo = c->topo.data(); io.hqp = 1;
-    std::vector<real_t> lds(LdsR<39, 34, 4>::rtotal + 64);
-    std::vector<int> ilds(64);
-    for (int b = 0; b < B; b++) {
-        Thr th{0};
-        if (c->su.n_levels == 1) cycle_instance_reduced<39, 34, 1, 1, TopoTocabi>(th, c->su, io, b, lds.data(), ilds.data());
-        else if (c->su.n_levels == 2) cycle_instance_reduced<39, 34, 2, 1, TopoTocabi>(th, c->su, io, b, lds.data(), ilds.data());
-        else if (c->su.n_levels == 3) cycle_instance_reduced<39, 34, 3, 1, TopoTocabi>(th, c->su, io, b, lds.data(), ilds.data());
-        else cycle_instance_reduced<39, 34, 4, 1, TopoTocabi>(th, c->su, io, b, lds.data(), ilds.data());
-    }
-    from_real(rdump, dump);
-    return 1;
-}
-
-static int g_emu_hqp = 1;
-static int g_emu_dense = 0;
-void emu_set_hqp(int hqp) { g_emu_hqp = hqp; }
-// 1: full-dynamics runs (1 - 4 levels) use the TopoGeneric (dense A^-1 sweep) instantiation instead of TOCABI's constant tree
-void emu_set_dense(int d) { g_emu_dense = d; }
-static const double *g_emu_custom = nullptr;
+int emu_lds_bytes_reduced(int nlv) { return lds_bytes<LdsR>(nlv); }
+int emu_lds_bytes_v2(int nlv) { return lds_bytes<Lds2>(nlv); }
+int emu_lds_bytes_compact(int nlv) { return lds_bytes<Lds3>(nlv); }
+int emu_lds_bytes_pair(int nlv) { return nlv == 1 ? Lds4<39, 34, 1>::total_bytes : Lds4<39, 34, 2>::total_bytes; }
 int emu_add_custom_task(EmuCtx *c, int level, int dof) { return setup_add_custom_task(c->su, level, dof, c->err) ? 1 : 0; }
-void emu_set_custom(const double *J) { g_emu_custom = J; }
-static const double *g_emu_traj = nullptr, *g_emu_ctime = nullptr;
 void emu_set_traj(EmuCtx *c, int level, int link_index, int slot, const double *gains15) {
     c->su.t_traj_slot[level][link_index] = slot;
     if (slot + 1 > c->su.n_traj) c->su.n_traj = slot + 1;
     for (int a = 0; a < 15; a++) c->su.t_gain[level][link_index][a] = gains15[a];
 }
-void emu_set_traj_data(const double *traj, const double *ctime) { g_emu_traj = traj; g_emu_ctime = ctime; }
-static int g_emu_warm = 0;
-void emu_set_warm(int on) { g_emu_warm = on; }
-// 1: the lean build on the compact LDS map (Lds3: the throughput kernel of batches beyond four instances per CU); LDS is
-// poisoned with NaN before every instance, so a read of a block that nothing has written yet shows up in the result
-static int g_emu_compact = 0;
-void emu_set_compact(int on) { g_emu_compact = on; }
-int emu_lds_bytes_pair(int nlv) { return nlv == 1 ? Lds4<39, 34, 1>::total_bytes : Lds4<39, 34, 2>::total_bytes; }
-int emu_lds_bytes_compact(int nlv) { return nlv == 1 ? Lds3<39, 34, 1>::total_bytes : nlv == 2 ? Lds3<39, 34, 2>::total_bytes : nlv == 3 ? Lds3<39, 34, 3>::total_bytes : Lds3<39, 34, 4>::total_bytes; }
-static const double *g_emu_qdot = nullptr;
-void emu_set_qdot(const double *qd) { g_emu_qdot = qd; }
 
-int emu_run(EmuCtx *c, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau, double *wrench,
+// One cycle over a batch.  TOCABI (39, 34) runs every build; (37, 32), (23, 18) and (43, 38) -- the sizes tests/test_model_packs.py
+// builds from the TOCABI fixture (43 / 38: four links added to a hand), the kernel packs of dwbc_pack.hip -- run the extras build on
+// TopoGeneric with two task levels (they have no constant tree, so EMU_EXTRAS means the same there), and the general-contact kernel
+// runs the first three sizes (wrench: B x 18; a level of more than 6 dof: the TG = 12 instantiation, TOCABI's size only).
+int emu_run(EmuCtx *c, const EmuRun *r, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau, double *wrench,
             int *status, int *diag, double *dump) {
+    const int n = c->model.ndof, nb = c->model.nb, nlv = c->su.n_levels;
+    const bool tocabi = n == 39 && nb == 34;
+    EmuBuild build = r->build;
+    const bool wide_tasks = build == EMU_GC && setup_wide_tasks(c->su);
+    if (build == EMU_GC) {
+        if (!(tocabi || (n == 37 && nb == 32) || (n == 23 && nb == 18))) { c->err = "emu_run_gc: instantiated for (39, 34), (37, 32) and (23, 18)"; return 0; }
+        if (wide_tasks && !tocabi) { c->err = "emu_run_gc: task levels of more than 6 dof are instantiated for (39, 34)"; return 0; }
+    } else if (!tocabi) {
+        if (build != EMU_EXTRAS && build != EMU_EXTRAS_GENERIC) { c->err = "emu is instantiated for TOCABI (39 dof) only"; return 0; }
+        if (nlv != 2) { c->err = "emu_run_other: two task levels"; return 0; }
+        if (!((n == 37 && nb == 32) || (n == 23 && nb == 18) || (n == 43 && nb == 38))) { c->err = "emu_run_other: instantiated for (37, 32), (23, 18) and (43, 38)"; return 0; }
+        build = EMU_EXTRAS_GENERIC;
+    }
+    if (build == EMU_TWO_WAVE && dump) { c->err = "the paired (lean) build has no dump record"; return 0; }
+    if (build == EMU_TWO_WAVE && nlv > 2) { c->err = "the paired kernel is built for one and two task levels"; return 0; }
+    if (build == EMU_COMPACT && dump) { c->err = "the compact (lean) build has no dump record"; return 0; }
+
+    const Setup su = run_setup(c, r->inst_par);
+    EmuIO e(c, *r, B, q, flags, fstar, tau, wrench, status, diag, dump);
+    if (build == EMU_GC) e.io.wrench_ld = 18;
+    const BatchIO &io = e.io;
+    const Thr th{0};
+    std::vector<int> ilds(64);
+    int *iL = ilds.data();
+    switch (build) {
+    case EMU_EXTRAS:
+        with_levels(nlv, [&](auto k) {
+            constexpr int NLV = decltype(k)::value;
+            each_instance(B, Lds2<39, 34, 4>::total, [&](int b, real_t *L) { cycle_instance_v2<39, 34, NLV, 1, true, TopoTocabi>(th, su, io, b, L, iL); });
+        });
+        break;
+    case EMU_EXTRAS_GENERIC:  // the dense A^-1 sweep instead of TOCABI's constant tree
+        if (tocabi) with_levels(nlv, [&](auto k) {
+            constexpr int NLV = decltype(k)::value;
+            each_instance(B, Lds2<39, 34, 4>::total, [&](int b, real_t *L) { cycle_instance_v2<39, 34, NLV, 1, true, TopoGeneric>(th, su, io, b, L, iL); });
+        });
+        else if (n == 37) each_instance(B, Lds2<37, 32, 2>::total, [&](int b, real_t *L) { cycle_instance_v2<37, 32, 2, 1, true, TopoGeneric>(th, su, io, b, L, iL); });
+        else if (n == 23) each_instance(B, Lds2<23, 18, 2>::total, [&](int b, real_t *L) { cycle_instance_v2<23, 18, 2, 1, true, TopoGeneric>(th, su, io, b, L, iL); });
+        else each_instance(B, Lds2<43, 38, 2>::total, [&](int b, real_t *L) { cycle_instance_v2<43, 38, 2, 1, true, TopoGeneric>(th, su, io, b, L, iL); });
+        break;
+    case EMU_COMPACT:  // the lean build on the compact LDS map (Lds3: the throughput kernel of batches beyond four instances per CU)
+        with_levels(nlv, [&](auto k) {
+            constexpr int NLV = decltype(k)::value;
+            each_instance(B, Lds2<39, 34, 4>::total, [&](int b, real_t *L) { cycle_instance_v2<39, 34, NLV, 1, false, TopoTocabi, true>(th, su, io, b, L, iL); });
+        });
+        break;
+    case EMU_TWO_WAVE:  // the paired kernel of dwbc_cycle2p.h with both roles run one after the other in every phase (wave = -1)
+        if (nlv == 1) each_instance(B, Lds4<39, 34, 1>::total, [&](int b, real_t *L) { cycle_instance_v2p<39, 34, 1, 1, TopoTocabi>(-1, th, su, io, b, L); });
+        else each_instance(B, Lds4<39, 34, 2>::total, [&](int b, real_t *L) { cycle_instance_v2p<39, 34, 2, 1, TopoTocabi>(-1, th, su, io, b, L); });
+        break;
+    case EMU_REDUCED:
+        with_levels(nlv, [&](auto k) {
+            constexpr int NLV = decltype(k)::value;
+            each_instance(B, LdsR<39, 34, 4>::rtotal, [&](int b, real_t *L) { cycle_instance_reduced<39, 34, NLV, 1, TopoTocabi>(th, su, io, b, L, iL); });
+        });
+        break;
+    case EMU_GC:  // the general-contact kernel of dwbc_cycle_gc.h (up to three active contacts)
+        if (wide_tasks) each_instance(B, LdsG<39, 34, 3, kMaxTaskDofWide>::total, [&](int b, real_t *L) { cycle_instance_gc<39, 34, 3, 1, kMaxTaskDofWide>(th, su, io, b, L); });
+        else if (n == 39) each_instance(B, LdsG<39, 34, 3>::total, [&](int b, real_t *L) { cycle_instance_gc<39, 34, 3, 1>(th, su, io, b, L); });
+        else if (n == 37) each_instance(B, LdsG<37, 32, 3>::total, [&](int b, real_t *L) { cycle_instance_gc<37, 32, 3, 1>(th, su, io, b, L); });
+        else each_instance(B, LdsG<23, 18, 3>::total, [&](int b, real_t *L) { cycle_instance_gc<23, 18, 3, 1>(th, su, io, b, L); });
+        break;
+    default:
+        c->err = "emu_run: unknown build";
+        return 0;
+    }
+    e.finish();
+    return 1;
+}
+
+// the redistribution kernel for a caller-supplied torque (dwbc_redistribute.h); task levels play no part in it.  As in the product
+// (dwbc_kernels.h) it is fp64 only: DWBC_NO_REDIST_KERNEL leaves it out of the fp32 library
+#ifndef DWBC_NO_REDIST_KERNEL
+int emu_redist_lds_bytes() { return LdsRd<39, 34>::total_bytes; }
+int emu_run_redist(EmuCtx *c, int B, const double *q, const unsigned char *flags, const double *fstar, const double *tau_in, const double *inst_par,
+                   double *tau, double *cf, double *wrench, int *status) {
     if (c->model.ndof != 39 || c->model.nb != 34) { c->err = "emu is instantiated for TOCABI (39 dof) only"; return 0; }
-    const int n = 39, m = 33;
-    const size_t D = DumpLayout::make(n).total;
-    (void)m;
-    auto rb = to_real(c->body.data(), c->body.size());
-    std::vector<real_t> rdump(dump ? (size_t)B * D : 0);
-    BatchIO io{};
-    io.B = B;
-    io.q = q;
-    io.qdot = g_emu_qdot;
-    io.traj = c->su.n_traj > 0 ? g_emu_traj : nullptr;
-    io.ctime = g_emu_ctime;
-    io.custom_J = c->su.n_custom > 0 ? g_emu_custom : nullptr;
-    io.flags = flags;
-    io.fstar = fstar;
-    io.tau = tau;
-    io.wrench = wrench;
-    io.status = status;
-    io.diag = diag;
-    io.dump = dump ? rdump.data() : nullptr;
-    io.body = rb.data();
-    io.topo = c->topo.data();
-    io.hqp = g_emu_hqp;
-    io.warm = g_emu_warm;
-    std::vector<real_t> lds(Lds2<39, 34, 4>::total + 64);
-    std::vector<int> ilds(64);
-    if (g_emu_compact == 2) {
-        // the paired kernel of dwbc_cycle2p.h with both roles run one after the other in every phase (wave = -1), LDS poisoned
-        if (dump) { c->err = "the paired (lean) build has no dump record"; return 0; }
-        if (c->su.n_levels > 2) { c->err = "the paired kernel is built for one and two task levels"; return 0; }
-        std::vector<real_t> l4(Lds4<39, 34, 2>::total + 64);
-        for (int b = 0; b < B; b++) {
-            Thr th{0};
-            std::fill(l4.begin(), l4.end(), std::numeric_limits<real_t>::quiet_NaN());
-            if (c->su.n_levels == 1) cycle_instance_v2p<39, 34, 1, 1, TopoTocabi>(-1, th, c->su, io, b, l4.data());
-            else cycle_instance_v2p<39, 34, 2, 1, TopoTocabi>(-1, th, c->su, io, b, l4.data());
-        }
-        return 1;
-    }
-    if (g_emu_compact) {
-        if (dump) { c->err = "the compact (lean) build has no dump record"; return 0; }
-        io.diag = diag;
-        for (int b = 0; b < B; b++) {
-            Thr th{0};
-            const real_t nan_ = std::numeric_limits<real_t>::quiet_NaN();
-            auto run = [&](auto nlv) {
-                constexpr int NLV = decltype(nlv)::value;
-                std::fill(lds.begin(), lds.end(), nan_);
-                cycle_instance_v2<39, 34, NLV, 1, false, TopoTocabi, true>(th, c->su, io, b, lds.data(), ilds.data());
-            };
-            if (c->su.n_levels == 1) run(std::integral_constant<int, 1>{});
-            else if (c->su.n_levels == 2) run(std::integral_constant<int, 2>{});
-            else if (c->su.n_levels == 3) run(std::integral_constant<int, 3>{});
-            else run(std::integral_constant<int, 4>{});
-        }
-        return 1;
-    }
-    for (int b = 0; b < B; b++) {
-        Thr th{0};
-        auto run = [&](auto nlv) {
-            constexpr int NLV = decltype(nlv)::value;
-            if (g_emu_dense) cycle_instance_v2<39, 34, NLV, 1, true, TopoGeneric>(th, c->su, io, b, lds.data(), ilds.data());
-            else cycle_instance_v2<39, 34, NLV, 1, true, TopoTocabi>(th, c->su, io, b, lds.data(), ilds.data());
-        };
-        if (c->su.n_levels == 1) run(std::integral_constant<int, 1>{});
-        else if (c->su.n_levels == 2) run(std::integral_constant<int, 2>{});
-        else if (c->su.n_levels == 3) run(std::integral_constant<int, 3>{});
-        else run(std::integral_constant<int, 4>{});
-    }
-    from_real(rdump, dump);
+    EmuRun r{};
+    r.hqp = 1;
+    r.inst_par = inst_par;
+    const Setup su = run_setup(c, inst_par);
+    EmuIO e(c, r, B, q, flags, fstar, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const RedistIO rio{tau_in, tau, cf, wrench, status};
+    each_instance(B, LdsRd<39, 34>::total, [&](int b, real_t *L) { redistribute_instance<39, 34, 1, TopoTocabi>(Thr{0}, su, e.io, rio, b, L); });
     return 1;
 }
-
-// the general-contact kernel of dwbc_cycle_gc.h (up to three active contacts; wrench: B x 18), LDS poisoned per instance
-int emu_run_gc(EmuCtx *c, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau, double *wrench,
-               int *status, int *diag) {
-    const int n_ = c->model.ndof, nb_ = c->model.nb;
-    if (!((n_ == 39 && nb_ == 34) || (n_ == 37 && nb_ == 32) || (n_ == 23 && nb_ == 18))) { c->err = "emu_run_gc: instantiated for (39, 34), (37, 32) and (23, 18)"; return 0; }
-    auto rb = to_real(c->body.data(), c->body.size());
-    BatchIO io{};
-    io.B = B;
-    io.q = q;
-    io.flags = flags;
-    io.fstar = fstar;
-    io.tau = tau;
-    io.wrench = wrench;
-    io.wrench_ld = 18;
-    io.status = status;
-    io.diag = diag;
-    io.body = rb.data();
-    io.topo = c->topo.data();
-    io.hqp = 1;
-    const bool wide_tasks = setup_wide_tasks(c->su);  // a level of more than 6 dof: the TG = 12 instantiation (TOCABI's size)
-    if (wide_tasks && n_ != 39) { c->err = "emu_run_gc: task levels of more than 6 dof are instantiated for (39, 34)"; return 0; }
-    std::vector<real_t> lds(LdsG<39, 34, 3, kMaxTaskDofWide>::total + 64);
-    static_assert(LdsG<37, 32, 3>::total <= LdsG<39, 34, 3>::total && LdsG<23, 18, 3>::total <= LdsG<39, 34, 3>::total &&
-                  LdsG<39, 34, 3>::total <= LdsG<39, 34, 3, kMaxTaskDofWide>::total, "one buffer");
-    for (int b = 0; b < B; b++) {
-        std::fill(lds.begin(), lds.end(), std::numeric_limits<real_t>::quiet_NaN());
-        if (wide_tasks) cycle_instance_gc<39, 34, 3, 1, kMaxTaskDofWide>(Thr{0}, c->su, io, b, lds.data());
-        else if (n_ == 39) cycle_instance_gc<39, 34, 3, 1>(Thr{0}, c->su, io, b, lds.data());
-        else if (n_ == 37) cycle_instance_gc<37, 32, 3, 1>(Thr{0}, c->su, io, b, lds.data());
-        else cycle_instance_gc<23, 18, 3, 1>(Thr{0}, c->su, io, b, lds.data());
-    }
-    return 1;
-}
-
-// ---- other model sizes (the kernel packs of dwbc_pack.hip): the same source instantiated for (37, 32) and (23, 18), two task
-//      levels, TopoGeneric -- the sizes tests/test_model_packs.py builds from the TOCABI fixture (43 / 38: four links added to a hand)
-}  // extern "C"
-template <int N, int NB>
-static void emu_run_size(EmuCtx *c, BatchIO &io, int B) {
-    std::vector<real_t> lds(Lds2<N, NB, 2>::total + 64);
-    std::vector<int> ilds(64);
-    for (int b = 0; b < B; b++) cycle_instance_v2<N, NB, 2, 1, true, TopoGeneric>(Thr{0}, c->su, io, b, lds.data(), ilds.data());
-}
-extern "C" {
-int emu_run_other(EmuCtx *c, int B, const double *q, const unsigned char *flags, const double *fstar, double *tau, double *wrench,
-                  int *status, int *diag, double *dump) {
-    const int n = c->model.ndof, nb = c->model.nb;
-    if (c->su.n_levels != 2) { c->err = "emu_run_other: two task levels"; return 0; }
-    const size_t D = DumpLayout::make(n).total;
-    auto rb = to_real(c->body.data(), c->body.size());
-    std::vector<real_t> rdump(dump ? (size_t)B * D : 0);
-    BatchIO io{};
-    io.B = B; io.q = q; io.flags = flags; io.fstar = fstar; io.tau = tau; io.wrench = wrench; io.status = status;
-    io.diag = diag; io.dump = dump ? rdump.data() : nullptr; io.body = rb.data(); io.topo = c->topo.data(); io.hqp = 1;
-    if (n == 37 && nb == 32) emu_run_size<37, 32>(c, io, B);
-    else if (n == 23 && nb == 18) emu_run_size<23, 18>(c, io, B);
-    else if (n == 43 && nb == 38) emu_run_size<43, 38>(c, io, B);
-    else { c->err = "emu_run_other: instantiated for (37, 32), (23, 18) and (43, 38)"; return 0; }
-    from_real(rdump, dump);
-    return 1;
-}
+#endif
 
 // ---- generic HQP class (dwbc_hqp.h): levels described by (m, e, has_cost); per-instance records laid out by hqp_layout()
 struct EmuHqp {

@@ -1,5 +1,5 @@
 """not-gpu: per-instance torque limits and contact cone constants (BatchIO::inst_par) in host emulation of the one-wave cycle and of the
-redistribution kernel (tests/emu/emu_inst_par.cpp: one "thread" per workgroup, LDS NaN-poisoned before every instance) against the
+redistribution kernel (tests/emu/emu_cycle.cpp: one "thread" per workgroup, LDS NaN-poisoned before every instance) against the
 restatement with one set-up per instance.
 
 Inputs and bars: tests/inst_par_cases.py (states of synth_batch seed 7, yaw, mixed support; limits TAU_LIM * U(0.15, 0.5), contact
@@ -11,14 +11,14 @@ import pytest
 from tests import cases
 from tests import inst_par_cases as ic
 from tests import redist_cases as rc
-from tests.emu.emu_inst_par import EmuInstPar
+from tests.emu.emu import Emu
 
 B = 48
 
 
 @pytest.fixture(scope="module")
 def emu():
-    return EmuInstPar(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM, tasks=cases.TASKS_2LEVEL)
+    return Emu(cases.URDF, cases.CONTACTS_2, cases.TASKS_2LEVEL, cases.TAU_LIM)
 
 
 @pytest.mark.parametrize("compact", [False, True], ids=["extras", "compact_lean"])
@@ -27,7 +27,7 @@ def test_cycle_matches_restatement(emu, lim, con, compact):
     q, flags, fstar = ic.states(B)
     ref = ic.reference(B, lim, con)
     ic.check_premises(ref, ic.reference(B, False, False), f"lim={lim} con={con}")
-    got = emu.run_cycle(q, flags, fstar, ic.record(B, ic.limits(B) if lim else None, ic.contact_consts(B) if con else None), compact=compact)
+    got = emu.run(q, flags, fstar, inst_par=ic.record(B, ic.limits(B) if lim else None, ic.contact_consts(B) if con else None), compact=compact)
     ic.compare(got["tau"], got["wrench"], got["status"], ref, f"lim={lim} con={con} compact={compact}")
 
 
@@ -35,8 +35,8 @@ def test_record_without_a_batch_wide_limit(emu):
     """the torque rows exist exactly as after SetTorqueLimit: a set-up that never had a limit gives the same bits under the same record"""
     q, flags, fstar = ic.states(B)
     rec = ic.record(B, ic.limits(B), ic.contact_consts(B))
-    nolim = EmuInstPar(cases.URDF, cases.CONTACTS_2, None, tasks=cases.TASKS_2LEVEL)
-    a, b = emu.run_cycle(q, flags, fstar, rec), nolim.run_cycle(q, flags, fstar, rec)
+    nolim = Emu(cases.URDF, cases.CONTACTS_2, cases.TASKS_2LEVEL, None)
+    a, b = emu.run(q, flags, fstar, inst_par=rec), nolim.run(q, flags, fstar, inst_par=rec)
     for k in ("tau", "wrench", "status"):
         assert (a[k] == b[k]).all(), k
     ra, rb = emu.run_redist(q, flags, rc.state_set(B, True, "mixed")["tau_in"], rec), nolim.run_redist(q, flags, rc.state_set(B, True, "mixed")["tau_in"], rec)
@@ -47,8 +47,8 @@ def test_record_without_a_batch_wide_limit(emu):
 @pytest.mark.parametrize("compact", [False, True], ids=["extras", "compact_lean"])
 def test_batch_wide_record_is_bit_equal_to_none(emu, compact):
     q, flags, fstar = ic.states(B)
-    plain = emu.run_cycle(q, flags, fstar, None, compact=compact)
-    same = emu.run_cycle(q, flags, fstar, ic.record(B, None, None), compact=compact)
+    plain = emu.run(q, flags, fstar, inst_par=None, compact=compact)
+    same = emu.run(q, flags, fstar, inst_par=ic.record(B, None, None), compact=compact)
     assert (plain["status"] == 1).mean() >= 0.9
     for k in ("tau", "wrench", "status"):
         assert (plain[k] == same[k]).all(), k

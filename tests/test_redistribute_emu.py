@@ -1,5 +1,5 @@
 """not-gpu: the redistribution kernel for a caller-supplied torque (libdwbc_amd/csrc/dwbc_redistribute.h) in host emulation
-(tests/emu/emu_redist.cpp: one "thread" per workgroup, LDS NaN-poisoned before every instance) against the numpy restatement.
+(tests/emu/emu_cycle.cpp: one "thread" per workgroup, LDS NaN-poisoned before every instance) against the numpy restatement.
 
 Inputs and bars: tests/redist_cases.py (states of synth_batch seed 7, tau_in = the restatement's full-cycle torque pushed along the
 contact null space by d = 10 N(0, I6)); 1e-6 Nm on the torque and on DWBC_REDIST_CF . NwJw, 1e-5 N on both wrench rows."""
@@ -8,14 +8,14 @@ import pytest
 
 from tests import cases
 from tests import redist_cases as rc
-from tests.emu.emu_redist import EmuRedist
+from tests.emu.emu import Emu
 
 B = 32
 
 
 @pytest.fixture(scope="module")
 def emu():
-    return EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM)
+    return Emu(cases.URDF, cases.CONTACTS_2, (), cases.TAU_LIM)
 
 
 @pytest.mark.parametrize("yaw", [False, True], ids=["flat", "yaw"])
@@ -23,14 +23,14 @@ def emu():
 def test_emulation_matches_restatement(emu, yaw, mode):
     ref = rc.state_set(B, yaw, mode)
     rc.check_premises(ref)
-    got = emu.run(ref["q"], ref["flags"], ref["tau_in"])
+    got = emu.run_redist(ref["q"], ref["flags"], ref["tau_in"])
     rc.compare(got, ref)
 
 
 def test_feasible_input_is_left_alone(emu):
     """tau_in = the cycle's own torque: nothing to redistribute, the correction is zero and both wrench rows are the same wrench"""
     ref = rc.state_set(B, False, "LR")
-    got = emu.run(ref["q"], ref["flags"], ref["tau_feasible"])
+    got = emu.run_redist(ref["q"], ref["flags"], ref["tau_feasible"])
     assert (got["status"] == 1).all()
     assert np.abs(got["tau"]).max() <= 1e-6
     assert (got["wrench"][:, 0] == got["wrench"][:, 1]).all() and np.abs(got["wrench"][:, 0]).max(axis=1).min() > 100.0
@@ -45,7 +45,7 @@ def test_single_support_and_no_contact(emu):
     ref = rc.state_set(B, True, "mixed")
     flags = ref["flags"].copy()
     flags[::5] = 0  # every fifth instance in the air
-    got = emu.run(ref["q"], flags, ref["tau_in"])
+    got = emu.run_redist(ref["q"], flags, ref["tau_in"])
     nact = flags.sum(axis=1)
     assert (nact == 0).any() and (nact == 1).any() and (nact == 2).any()
     assert (got["status"] == np.where(nact == 2, ref["status"], 1)).all()
@@ -63,12 +63,12 @@ def test_single_support_and_no_contact(emu):
 
 
 def test_more_than_two_flags_fail_the_instance():
-    e4 = EmuRedist(cases.URDF, cases.CONTACTS_4, cases.TAU_LIM)
+    e4 = Emu(cases.URDF, cases.CONTACTS_4, (), cases.TAU_LIM)
     ref = rc.state_set(B, False, "LR")
     flags = np.zeros((B, 4), np.uint8)
     flags[:, :2] = 1
     flags[1::2, 2] = 1  # a third flag on every other instance
-    got = e4.run(ref["q"], flags, ref["tau_in"])
+    got = e4.run_redist(ref["q"], flags, ref["tau_in"])
     three = flags.sum(axis=1) == 3
     assert (got["status"][three] == 0).all() and (got["status"][~three] == ref["status"][~three]).all()
     for k in ("tau", "cf", "wrench"):
@@ -80,13 +80,13 @@ def test_more_than_two_flags_fail_the_instance():
 def test_task_levels_play_no_part():
     """a set-up that carries task levels (a cycle batch's, the facade's) gives bit-identical answers; no torque limit: cone rows only"""
     ref = rc.state_set(B, False, "LR")
-    plain = EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM).run(ref["q"], ref["flags"], ref["tau_in"])
-    tasked = EmuRedist(cases.URDF, cases.CONTACTS_2, cases.TAU_LIM, tasks=cases.TASKS_2LEVEL).run(ref["q"], ref["flags"], ref["tau_in"])
+    plain = Emu(cases.URDF, cases.CONTACTS_2, (), cases.TAU_LIM).run_redist(ref["q"], ref["flags"], ref["tau_in"])
+    tasked = Emu(cases.URDF, cases.CONTACTS_2, cases.TASKS_2LEVEL, cases.TAU_LIM).run_redist(ref["q"], ref["flags"], ref["tau_in"])
     for k in ("tau", "cf", "wrench", "status"):
         assert (plain[k] == tasked[k]).all(), k
-    nolim = EmuRedist(cases.URDF, cases.CONTACTS_2, None).run(ref["q"], ref["flags"], ref["tau_in"])
+    nolim = Emu(cases.URDF, cases.CONTACTS_2, (), None).run_redist(ref["q"], ref["flags"], ref["tau_in"])
     assert (nolim["status"] == 1).all() and np.isfinite(nolim["tau"]).all()
 
 
 def test_lds_map_is_in_the_compact_class(emu):
-    assert emu.lds_bytes() <= 20480  # eight workgroups per CU
+    assert emu.redist_lds_bytes() <= 20480  # eight workgroups per CU
