@@ -92,7 +92,9 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
     PL(real_t, gnv);        // |g| before the normalisation (1 for a zero row): normalised slack * gnv = slack of the row as given
     PL(real_t, u);          // slot lanes: multiplier
     PL(int, akey);          // slot lanes: (owner lane << 1) | side
-    PL(int, actf);          // bit0: hi side in the working set, bit1: lo side
+    PL(real_t, ehi);        // the bounds the pick sees: R.hi / R.lo, and +inf for a side that is absent or in the working set (set on add,
+    PL(real_t, elo);        // restored on drop), so the slack pass needs no mask: inf -/+ d is inf again.  R.hi / R.lo stay as given
+    PL(bool, rok);          // slot lanes: the ratio test has an entry here
     PL(int, slotbit);       // 1 << slot for lanes 16..27, else 0
     PL(real_t, val);
     PL(int, key);
@@ -124,10 +126,11 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
         }
         if (LV(R.hi) < DWBC_QP_INF && !zrow) LV(R.hi) *= rg;
         if (LV(R.lo) < DWBC_QP_INF && !zrow) LV(R.lo) *= rg;
+        LV(ehi) = LV(R.hi) >= DWBC_QP_INF ? DWBC_QP_INF : LV(R.hi);
+        LV(elo) = LV(R.lo) >= DWBC_QP_INF ? DWBC_QP_INF : LV(R.lo);
         LV(d) = real_t(0.0);
         LV(u) = real_t(0.0);
         LV(akey) = 0;
-        LV(actf) = 0;
         LV(slotbit) = (lane >= SB && lane < SB + NV) ? (1 << (lane - SB)) : 0;
         LV(m) = real_t(0.0);
         LV(dz) = real_t(0.0);
@@ -137,6 +140,7 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
     int used = 0, q = 0, it = 0, status = 1, p = 0, side = 0, kmin = 0;
     bool pick = true;
     real_t up = real_t(0.0), worst = real_t(0.0);
+    real_t sp = real_t(0.0);  // slack of the violated side (negative): what the pick returned, recomputed after a partial step
     int wid[QN], wpos = QN;
     if (WS && warm) {
 #pragma unroll
@@ -153,9 +157,9 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
                 wpos++;
                 if (id < 0) continue;
                 LANES {
-                    const bool mh = LV(R.id_hi) == id && !(LV(actf) & 1) && LV(R.hi) < DWBC_QP_INF;
-                    const bool ml = LV(R.id_lo) == id && !(LV(actf) & 2) && LV(R.lo) < DWBC_QP_INF;
-                    LV(val) = mh ? LV(R.hi) - LV(d) : (ml ? LV(R.lo) + LV(d) : DWBC_QP_INF);
+                    const bool mh = LV(R.id_hi) == id && LV(ehi) < DWBC_QP_INF;
+                    const bool ml = LV(R.id_lo) == id && LV(elo) < DWBC_QP_INF;
+                    LV(val) = mh ? LV(ehi) - LV(d) : (ml ? LV(elo) + LV(d) : DWBC_QP_INF);
                     LV(key) = (lane << 1) | (ml ? 1 : 0);
                 }
                 int pl;
@@ -168,13 +172,14 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
                 p = kmin >> 1;
                 side = kmin & 1;
                 up = real_t(0.0);
+                sp = worst;
                 pick = false;
             }
         }
         if (pick) {
             LANES {
-                const real_t sh = ((LV(actf) & 1) || LV(R.hi) >= DWBC_QP_INF) ? DWBC_QP_INF : LV(R.hi) - LV(d);
-                const real_t sl = ((LV(actf) & 2) || LV(R.lo) >= DWBC_QP_INF) ? DWBC_QP_INF : LV(R.lo) + LV(d);
+                const real_t sh = LV(ehi) - LV(d);  // (inf - d = inf in both arithmetic types: |d| is far below one ulp of the sentinel)
+                const real_t sl = LV(elo) + LV(d);
                 const bool lo_side = sl < sh;
                 LV(val) = lo_side ? sl : sh;
                 LV(key) = (lane << 1) | (lo_side ? 1 : 0);
@@ -188,6 +193,7 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
             p = kmin >> 1;
             side = kmin & 1;
             up = real_t(0.0);
+            sp = worst;  // = (side ? lo + d : hi - d) of lane p, the very value the pick compared
             pick = false;
         }
         if (++it > max_iter) { status = 0; break; }
@@ -210,7 +216,6 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
 #pragma unroll
             for (int j = 0; j < NV; j++) s_ += LV(R.g)[j] * zu[j];
             LV(dz) = s_;  // change of g.x per unit step along z
-            LV(val) = side ? LV(R.lo) + LV(d) : LV(R.hi) - LV(d);
         }
         real_t zg = sgn * BCAST(dz, p);  // n.z = |z|^2
         // z = H n loses digits when n lies close to the span of the working set (the rows are unit vectors, so |z|^2 is the squared
@@ -234,20 +239,25 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
             }
             zg = sgn * BCAST(dz, p);
         }
-        const real_t sp = BCAST(val, p);       // slack of the violated side (negative)
         const bool zok = zg > (kF32 ? real_t(1e-10) : real_t(1e-20)) && q < nv;
         DWBC_QPT(2);
-        LANES {
-            const bool ok = (LV(slotbit) & used) && LV(m) > (kF32 ? real_t(1e-6) : real_t(1e-12));
-            LV(val) = ok ? LV(u) * fast_rcp(LV(m)) : DWBC_QP_INF;
-            LV(key) = lane;
-        }
-        real_t t1;
-        int l;
-        if constexpr (SB == 16) {
-            WAVE_ARGMIN_ROW1(val, key, t1, l);  // (the slot lanes are DPP row 1)
-        } else {
-            WAVE_ARGMIN(val, key, t1, l);       // every other lane holds +inf
+        LANES { LV(rok) = (LV(slotbit) & used) && LV(m) > (kF32 ? real_t(1e-6) : real_t(1e-12)); }
+        // ratio test over the slot lanes; with no entry (empty working set, no positive component of r) its outcome is t1 = inf
+        // and the arg-min with its broadcasts is left out
+        real_t t1 = DWBC_QP_INF;
+        int l = SB;
+        bool rany;
+        WAVE_ANY(rok, rany);
+        if (rany) {
+            LANES {
+                LV(val) = LV(rok) ? LV(u) * fast_rcp(LV(m)) : DWBC_QP_INF;
+                LV(key) = lane;
+            }
+            if constexpr (SB == 16) {
+                WAVE_ARGMIN_ROW1(val, key, t1, l);  // (the slot lanes are DPP row 1)
+            } else {
+                WAVE_ARGMIN(val, key, t1, l);       // every other lane holds +inf
+            }
         }
         const real_t t2 = zok ? -sp * fast_rcp(zg) : DWBC_QP_INF;
         const real_t tstep = t1 < t2 ? t1 : t2;
@@ -264,16 +274,15 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
         DWBC_QPT(3);
         if (full) {
             // working set += (p, side): H -= z z^T / zg, N^+ rows -= r_a z^T / zg, new N^+ row = z^T / zg
-            int slot = 0;
-#pragma unroll
-            for (int a = NV - 1; a >= 0; a--) slot = ((used >> a) & 1) ? slot : a;
+            const int slot = __builtin_ctz(~(unsigned)used);  // lowest free slot (q < nv <= NV: there is one)
             const real_t inv_ = fast_rcp(zg);
             LANES {
                 real_t coef = LV(m) * inv_;
                 if (lane == SB + slot) { coef = -inv_; LV(u) = up; LV(akey) = kmin; }
 #pragma unroll
                 for (int j = 0; j < NV; j++) LV(Mx)[j] -= coef * zu[j];
-                if (lane == p) LV(actf) |= (side ? 2 : 1);
+                LV(ehi) = ((lane << 1) == kmin) ? DWBC_QP_INF : LV(ehi);  // (kmin = (p << 1) | side)
+                LV(elo) = (((lane << 1) | 1) == kmin) ? DWBC_QP_INF : LV(elo);
             }
             used |= 1 << slot;
             q++;
@@ -302,11 +311,15 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
 #pragma unroll
                 for (int j = 0; j < NV; j++) LV(Mx)[j] = (lane == l) ? real_t(0.0) : LV(Mx)[j] - coef * rho[j];
                 if (lane == l) LV(u) = real_t(0.0);
-                if (lane == (kl >> 1)) LV(actf) &= ~((kl & 1) ? 2 : 1);
+                LV(ehi) = ((lane << 1) == kl) ? LV(R.hi) : LV(ehi);  // (a side that was in the working set has a finite bound)
+                LV(elo) = (((lane << 1) | 1) == kl) ? LV(R.lo) : LV(elo);
             }
             WSYNC();
             used &= ~(1 << (l - SB));
             q--;
+            // the partial step moved d: the slack of the violated side again, as the pick would compute it
+            LANES { LV(val) = side ? LV(R.lo) + LV(d) : LV(R.hi) - LV(d); }
+            sp = BCAST(val, p);
         }
         DWBC_QPT(4);
     }

@@ -198,6 +198,12 @@ DWBC_WDEV real_t pick12(const real_t *a, int lane) {
         out_v = (val)[0];                                                                          \
         for (int l_ = 1; l_ < 64; l_++) out_v += (val)[l_];                                        \
     } while (0)
+// does a per-lane flag hold in any lane (uniform result)
+#define WAVE_ANY(flag, out_b)                                                                      \
+    do {                                                                                           \
+        out_b = false;                                                                             \
+        for (int l_ = 0; l_ < 64; l_++) out_b = out_b || (flag)[l_];                               \
+    } while (0)
 // exact arg-min over lanes 16..31 only
 #define WAVE_ARGMIN_ROW1(val, key, out_v, out_k)                                                   \
     do {                                                                                           \
@@ -345,6 +351,7 @@ __device__ __forceinline__ unsigned long long argmin_key(real_t v, int lane) {
         out_k = dwbc::readlane_i32((key), wl_);                                                    \
     } while (0)
 #define WAVE_ARGMIN_F32(val, out_lane) out_lane = dwbc::wave_argmin_f32(val)
+#define WAVE_ANY(flag, out_b) out_b = __ballot(flag) != 0ull
 #define WAVE_SUM(val, out_v) out_v = dwbc::wave_sum_f64(val)
 #define WAVE_PREFIX_A(arr, j) (arr)[(j)] = dwbc::wave_prefix_f64((arr)[(j)])
 #define WAVE_ARGMIN_ROW1(val, key, out_v, out_k)                                                   \

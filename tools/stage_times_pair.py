@@ -1,7 +1,8 @@
 """Diagnostic: timeline of the paired (two-wave) kernel of dwbc_cycle2p.h from the DWBC_STAGE_TIMERS build (make -C libdwbc_amd/csrc
 timed; DWBC_TIMED=1): when the main and the helper wave reach each of the five workgroup barriers, when the main wave leaves it
 (the later of the two plus the barrier itself), and the main wave's stamps of the last phase.  Shader cycles since kernel start,
-medians over the batch."""
+medians over the batch -- and, because all workgroups of such a batch are resident at once and the launch ends with its slowest
+instance, the maximum and the 99th percentile of the total, the total by the number of active-set steps, and the steps of every QP."""
 import os
 import sys
 
@@ -50,3 +51,20 @@ qn = ["post-loop", "slack + arg-min", "publish n, r, z", "step / drop", "commit"
 print("level-0 QP solver sections (cycles, summed over iterations):")
 for i, n in enumerate(qn):
     print(f"  {n:28s} {f[32 + i]:10.0f}")
+# ---- what governs the launch: the slowest instance, not the median one
+tot = d[:, 74 + 15].astype(np.float64)                      # last stamp of the main wave
+it = d[:, 4:9]                                              # DG_QP_ITER: task levels 0..3, redistribution in slot 4
+steps = it.sum(axis=1)
+print(f"total per instance: median {np.median(tot):.0f}  p99 {np.percentile(tot, 99):.0f}  max {tot.max():.0f}  (instance {int(tot.argmax())}: {int(steps[tot.argmax()])} steps)")
+print("total by active-set steps of the cycle (level 0 + level 1 + redistribution):")
+print(f"  {'steps':>5s} {'instances':>9s} {'median':>10s} {'max':>10s}")
+for s_ in np.unique(steps):
+    m_ = steps == s_
+    print(f"  {int(s_):5d} {int(m_.sum()):9d} {np.median(tot[m_]):10.0f} {tot[m_].max():10.0f}")
+print("steps per QP (instances):")
+for slot, n in ((0, "level 0"), (1, "level 1"), (4, "redistribution")):
+    v, c = np.unique(it[:, slot], return_counts=True)
+    print(f"  {n:15s} " + "  ".join(f"{int(a)}: {int(b)}" for a, b in zip(v, c)))
+sec = d[:, 90 + 32 : 90 + 32 + 5].astype(np.float64).sum(axis=1)  # the sections of the search (0..4) of the level-0 QP
+ok0 = it[:, 0] > 0
+print(f"level-0 QP: cycles per active-set step (search sections / steps): median {np.median(sec[ok0] / it[ok0, 0]):.0f}  max {(sec[ok0] / it[ok0, 0]).max():.0f}")
