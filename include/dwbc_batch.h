@@ -283,6 +283,34 @@ int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float
 /* name of the kernel dwbc_batch_redistribute launches on this batch ("" and dwbc_last_error when it would be refused) */
 const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b);
 
+/* ---- UpdateKinematics as a call of its own (reference include/dwbc.h, src/dwbc.cpp:279-371): what a caller reads between it and
+ * SetTaskSpace -- link_[i].xpos / rotm / v / w / jac_ and com_pos -- for a set of queried links, in one lean kernel (forward kinematics;
+ * no mass-matrix inverse, no contact stage, no QP).  A query is up to 16 entries (link, point in the link's frame); link =
+ * dwbc_model_num_links(m) is the synthetic COM link (com_pos, pelvis rotation, jac_com_, jac_com_ qdot), which takes no point.  Per entry:
+ *   DWBC_LQ_POS (3)      p_link + R_link point
+ *   DWBC_LQ_ROT (3 x 3)  R_link, row-major
+ *   DWBC_LQ_VEL (6)      [v of the point; w]; zero while the state was set without a qdot
+ *   DWBC_LQ_JAC (6 x n)  Jacobian of the point, rows [linear; angular] -- the layout dwbc_batch_set_custom_task takes; only if asked for
+ * all batch-major: (B, entries, ...).  The launch reads the state alone and names no buffer of dwbc_batch_solve or
+ * dwbc_batch_redistribute: their outputs, the dump record and the warm-start state stay as they are, the three may be called on one batch
+ * in any order.  dwbc_batch_copy_kinematics does not copy the query.
+ * Refused (dwbc_last_error): DWBC_F32 batches and a model without the kernel (built in for TOCABI's size, any tree), both at
+ * dwbc_batch_set_link_query; more than 16 entries, a link outside [0, num_links], a COM entry with a non-zero point -- the query and the
+ * outputs of the batch stay as they were; dwbc_batch_update_kinematics without a query; DWBC_LQ_JAC of a query set without Jacobians;
+ * dwbc_batch_get_link_query before the first launch of the query. */
+enum dwbc_link_query_output { DWBC_LQ_POS = 0, DWBC_LQ_ROT = 1, DWBC_LQ_VEL = 2, DWBC_LQ_JAC = 3 };
+/* points: n x 3 or NULL (all zero).  n = 0 drops the query.  A new query gets output buffers of its own size: bound ones are let go of
+ * (bind again), earlier results are gone. */
+int dwbc_batch_set_link_query(dwbc_batch *b, int n, const int32_t *links, const double *points, int want_jacobians);
+/* asynchronous on the batch's stream; uploads newer host mirrors of q and qdot first, like a solve */
+int dwbc_batch_update_kinematics(dwbc_batch *b);
+size_t dwbc_batch_link_query_bytes(const dwbc_batch *b, int what);  /* of all B instances; 0: no query, no such output */
+int dwbc_batch_get_link_query(dwbc_batch *b, int what, void *host_out, size_t bytes);  /* synchronises the stream */
+/* zero-copy: a caller-owned DEVICE buffer of dwbc_batch_link_query_bytes(b, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_link_query(dwbc_batch *b, int what, void *device_ptr);
+/* name of the kernel dwbc_batch_update_kinematics launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b);
+
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least
  * squares), optional cost 1/2 y^T H y; levels are solved in sequence inside the null space of the earlier equalities.  The

@@ -102,6 +102,13 @@ SYMBOLS = [
     ("dwbc_batch_redistribute", _i, [_vp, C.c_uint]),
     ("dwbc_batch_time_redistribute", _i, [_vp, C.c_uint, _i, C.POINTER(C.c_float)]),
     ("dwbc_batch_redistribute_kernel_name", C.c_char_p, [_vp]),
+    # link poses, velocities and Jacobians in a launch of their own
+    ("dwbc_batch_set_link_query", _i, [_vp, _i, _vp, _vp, _i]),
+    ("dwbc_batch_update_kinematics", _i, [_vp]),
+    ("dwbc_batch_link_query_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_batch_get_link_query", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_bind_link_query", _i, [_vp, _i, _vp]),
+    ("dwbc_batch_link_query_kernel_name", C.c_char_p, [_vp]),
     # per-instance torque limits and contact cone constants
     ("dwbc_batch_instance_param_stride", _i, [_vp]),
     ("dwbc_batch_set_instance_params", _i, [_vp, _vp]),

@@ -10,6 +10,8 @@
     tau = wbc.get("tau_total")
     wbc.set_torque_input(tau_policy); wbc.redistribute()   # CalcContactRedistribute(torque_input): any torque, its own lean kernel
     tau_policy + wbc.get("redist_tau")
+    wbc.set_link_query([0, 23], jacobians=True); wbc.update_kinematics()   # UpdateKinematics on its own: link_[i].xpos / rotm / v / w / jac_
+    wbc.link_states()["rot"]
 
 All arithmetic happens in libdwbc_hip.so (hand-written HIP, gfx950).  torch is only used, optionally, to own
 device buffers and streams (bind_tensor) and for torch.distributed in bench.py.
@@ -25,6 +27,7 @@ TASK_LINK_6D, TASK_LINK_6D_COM_FRAME, TASK_LINK_6D_CUSTOM_FRAME = 0, 1, 2
 TASK_LINK_POSITION, TASK_LINK_POSITION_COM_FRAME, TASK_LINK_POSITION_CUSTOM_FRAME = 3, 4, 5
 TASK_LINK_ROTATION, TASK_LINK_ROTATION_CUSTOM_FRAME = 6, 7
 SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
+LINK_QUERY_OUTPUTS = {"pos": 0, "rot": 1, "vel": 2, "jac": 3}  # enum dwbc_link_query_output
 
 
 def describe(index, n, n_contacts, fstar_total, max_active):
@@ -177,6 +180,7 @@ class Batch:
         self._keep = {}
         self._contact_consts = []  # (lx, ly, mu, mu_z) per registered contact and the batch-wide torque limit: what a missing half of
         self._tau_lim = None       # set_instance_params is filled from
+        self._link_query = (0, False)  # entries of set_link_query and whether it asked for Jacobians
 
     # ---- setup (shared by all instances)
     def add_contact(self, link, point, lx, ly, mu=0.2, mu_z=0.2, contact_type=CONTACT_6D):
@@ -401,6 +405,64 @@ class Batch:
 
     def redistribute_kernel_name(self):
         name = self._L.dwbc_batch_redistribute_kernel_name(self._h).decode()
+        if not name:
+            raise DwbcError(_lib.last_error())
+        return name
+
+    # ---- UpdateKinematics on its own: poses, velocities and Jacobians of queried links before any f* is set
+    def set_link_query(self, links, points=None, jacobians=False):
+        """The links update_kinematics() reports: up to 16 entries ``links`` with ``points`` (L, 3) in the links' frames (None: the
+        origins); ``model.link_id("COM")`` is the synthetic COM link, which takes no point.  ``jacobians``: also the 6 x n point Jacobians,
+        rows [linear; angular] -- what set_custom_task takes.  An empty list drops the query.  A new query has new output buffers: bind
+        tensors after it."""
+        l = np.ascontiguousarray(links, np.int32).reshape(-1)
+        p = None
+        if points is not None:
+            p = np.ascontiguousarray(points, np.float64)
+            assert p.shape == (len(l), 3), p.shape
+        _check(self._L.dwbc_batch_set_link_query(self._h, len(l), l.ctypes.data, p.ctypes.data if p is not None else None, 1 if jacobians else 0))
+        for k in LINK_QUERY_OUTPUTS:
+            self._keep.pop("link_query_" + k, None)
+        self._link_query = (len(l), bool(jacobians))
+
+    def update_kinematics(self):
+        """One lean kernel on the batch's stream, asynchronous: forward kinematics of the state (and of qdot, if set_state got one; zero
+        velocities otherwise) for the queried links.  Reads the state alone and leaves every output of solve() and redistribute() as it
+        is; the three may be called in any order."""
+        _check(self._L.dwbc_batch_update_kinematics(self._h))
+
+    def _link_query_shape(self, name):
+        n = self._link_query[0]
+        return {"pos": (self.B, n, 3), "rot": (self.B, n, 3, 3), "vel": (self.B, n, 6), "jac": (self.B, n, 6, self.n)}[name]
+
+    def link_states(self):
+        """dict of ``pos`` (B, L, 3), ``rot`` (B, L, 3, 3) row-major, ``vel`` (B, L, 6) = [v of the point; w] and, if the query asked for
+        them, ``jac`` (B, L, 6, n) of the last update_kinematics(); synchronises the stream"""
+        out = {}
+        for name, what in LINK_QUERY_OUTPUTS.items():
+            if name == "jac" and not self._link_query[1]:
+                continue
+            a = np.zeros(self._link_query_shape(name))
+            _check(self._L.dwbc_batch_get_link_query(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def bind_link_query(self, name, tensor):
+        """output ``name`` ("pos", "rot", "vel", "jac") of update_kinematics() into a caller-owned device tensor of float64, written in
+        place by every later launch; None: back to a buffer of the batch's own"""
+        what = LINK_QUERY_OUTPUTS[name]
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_link_query(self._h, what, None))
+            self._keep.pop("link_query_" + name, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = self._L.dwbc_batch_link_query_bytes(self._h, what)
+        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(self._L.dwbc_batch_bind_link_query(self._h, what, C.c_void_p(tensor.data_ptr())))
+        self._keep["link_query_" + name] = tensor
+
+    def link_query_kernel_name(self):
+        name = self._L.dwbc_batch_link_query_kernel_name(self._h).decode()
         if not name:
             raise DwbcError(_lib.last_error())
         return name

@@ -901,6 +901,15 @@ int dwbc_batch_time_solves(dwbc_batch *b, unsigned flags, int steps, float *ms) 
     return 1;
 }
 
+// device -> page-locked staging (asynchronous on the batch's stream, PCIe rate) -> the caller's memory
+static int read_back(dwbc_batch *b, const void *src, void *out, size_t nbytes) {
+    if (b->h_stage.size() < nbytes) b->h_stage.assign(nbytes);
+    HIP_OK(hipMemcpyAsync(b->h_stage.data(), src, nbytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    memcpy(out, b->h_stage.data(), nbytes);
+    return 1;
+}
+
 int dwbc_batch_get(dwbc_batch *b, int field, void *out, size_t bytes) {
     const fld::Row *r = fld::find(field);
     const size_t need = dwbc_batch_field_bytes(b, field);
@@ -908,14 +917,7 @@ int dwbc_batch_get(dwbc_batch *b, int field, void *out, size_t bytes) {
     if (bytes < need) return fail("output buffer too small");
     HIP_OK(hipSetDevice(b->device));
     HIP_OK(hipStreamSynchronize(b->stream));
-    // device -> page-locked staging (asynchronous on the batch's stream, PCIe rate) -> the caller's memory
-    auto d2h = [&](const void *src, size_t nbytes) -> int {
-        if (b->h_stage.size() < nbytes) b->h_stage.assign(nbytes);
-        HIP_OK(hipMemcpyAsync(b->h_stage.data(), src, nbytes, hipMemcpyDeviceToHost, b->stream));
-        HIP_OK(hipStreamSynchronize(b->stream));
-        memcpy(out, b->h_stage.data(), nbytes);
-        return 1;
-    };
+    auto d2h = [&](const void *src, size_t nbytes) -> int { return read_back(b, src, out, nbytes); };
     if (r->where == fld::kInSlot) {
         const void *src = b->buf[r->idx].d;
         return src || !r->absent ? d2h(src, need) : fail(r->absent);
@@ -952,6 +954,124 @@ int dwbc_batch_launch_info(const dwbc_batch *b, int *threads, int *lds) {
     if (threads) *threads = p.row ? p.threads : kNT;
     if (lds) *lds = p.row ? p.lds : 0;
     return 1;
+}
+
+// ---- UpdateKinematics on its own for a set of queried links: the lean kernel of dwbc_link_query.h
+static dwbc_plan::Plan link_query_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.link_query = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+
+// doubles per instance of one output of the query as it stands (0: no such output)
+static size_t link_query_elems(const dwbc_batch *b, int what) {
+    const size_t per[4] = {3, 9, 6, b->lq_jac ? (size_t)6 * b->n : 0};
+    return what >= DWBC_LQ_POS && what <= DWBC_LQ_JAC ? b->lq_n * per[what] : 0;
+}
+
+size_t dwbc_batch_link_query_bytes(const dwbc_batch *b, int what) { return (size_t)b->B * link_query_elems(b, what) * sizeof(double); }
+
+int dwbc_batch_set_link_query(dwbc_batch *b, int n, const int32_t *links, const double *points, int want_jacobians) {
+    if (n < 0 || n > kMaxLinkQuery) return fail("link query: at most 16 entries");
+    if (n > 0 && !links) return fail("link query: links is NULL");
+    const int nb = b->su.nb;
+    for (int i = 0; i < n; i++) {
+        if (links[i] < 0 || links[i] > nb) return fail("link query: link " + std::to_string(links[i]) + " is outside [0, " + std::to_string(nb) + "] (the last is the COM link)");
+        if (links[i] == nb && points && (points[3 * i] != 0.0 || points[3 * i + 1] != 0.0 || points[3 * i + 2] != 0.0))
+            return fail("link query: the COM link takes no point");
+    }
+    if (n > 0) {
+        const dwbc_plan::Plan p = link_query_plan(b);
+        if (!p.row) return fail(p.err);
+    }
+    // outputs of the new size, owned by the batch (a buffer bound for the old query may be too small for the new one); allocated here, so
+    // that dwbc_batch_update_kinematics itself allocates nothing
+    HIP_OK(hipSetDevice(b->device));
+    for (int w = DWBC_LQ_POS; w <= DWBC_LQ_JAC; w++) release(b->buf[fld::kLqPos + w]);  // (hipFree waits for the launches that write them)
+    b->lq_n = n;
+    b->lq_jac = n > 0 && want_jacobians != 0;
+    b->lq_ran = false;
+    for (int i = 0; i < n; i++) {
+        b->lq_link[i] = links[i];
+        for (int a = 0; a < 3; a++) b->lq_point[i][a] = points ? points[3 * i + a] : 0.0;
+    }
+    for (int w = DWBC_LQ_POS; w <= DWBC_LQ_JAC; w++)
+        if (const size_t bytes = dwbc_batch_link_query_bytes(b, w))
+            if (!ensure(b->buf[fld::kLqPos + w], bytes)) return 0;
+    return 1;
+}
+
+int dwbc_batch_update_kinematics(dwbc_batch *b) {
+    if (b->lq_n < 1) return fail("no link query: call dwbc_batch_set_link_query first");
+    const dwbc_plan::Plan p = link_query_plan(b);
+    if (!p.row) return fail(p.err);
+    HIP_OK(hipSetDevice(b->device));
+    bool queued = false;
+    for (const int slot : {fld::kQdot, fld::kQ})
+        if (!send(b, slot, &queued)) return 0;
+    if (queued && !mark_upload(b)) return 0;
+    BatchIO io{};  // the state and the model; no buffer of the cycle or of the redistribution is named
+    io.B = b->B;
+    io.q = b->dev<double>(fld::kQ);
+    io.qdot = b->dev<double>(fld::kQdot);
+    io.body = b->d_body;
+    io.topo = b->d_topo;
+    io.pair_swap_bit = -1;
+    LinkQueryIO lq{};
+    lq.n = b->lq_n;
+    lq.nb = b->su.nb;
+    lq.maxdepth = b->su.maxdepth;
+    lq.want_jac = b->lq_jac ? 1 : 0;
+    for (int i = 0; i < b->lq_n; i++) {
+        lq.link[i] = b->lq_link[i];
+        lq.has_com = lq.has_com || b->lq_link[i] == b->su.nb;
+        for (int a = 0; a < 3; a++) lq.point[i][a] = b->lq_point[i][a];
+    }
+    lq.pos = b->dev<double>(fld::kLqPos);
+    lq.rot = b->dev<double>(fld::kLqRot);
+    lq.vel = b->dev<double>(fld::kLqVel);
+    lq.jac = b->lq_jac ? b->dev<double>(fld::kLqJac) : nullptr;
+    void *args[] = {(void *)&io, (void *)&lq};
+    HIP_OK(hipLaunchKernel(p.row->fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    b->lq_ran = true;
+    return 1;
+}
+
+// why output `what` of the query cannot be named (nullptr: it can)
+static const char *link_query_refusal(const dwbc_batch *b, int what) {
+    if (what < DWBC_LQ_POS || what > DWBC_LQ_JAC) return "link query: unknown output";
+    if (b->lq_n < 1) return "no link query: call dwbc_batch_set_link_query first";
+    if (what == DWBC_LQ_JAC && !b->lq_jac) return "link query: set without Jacobians (dwbc_batch_set_link_query with want_jacobians = 1)";
+    return nullptr;
+}
+
+int dwbc_batch_get_link_query(dwbc_batch *b, int what, void *out, size_t bytes) {
+    if (const char *why = link_query_refusal(b, what)) return fail(why);
+    if (!b->lq_ran) return fail("no link-query output yet: call dwbc_batch_update_kinematics first");
+    const size_t need = dwbc_batch_link_query_bytes(b, what);
+    if (bytes < need) return fail("output buffer too small");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kLqPos + what].d, out, need);
+}
+
+int dwbc_batch_bind_link_query(dwbc_batch *b, int what, void *p) {
+    if (const char *why = link_query_refusal(b, what)) return fail(why);
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kLqPos + what];
+    release(u);
+    b->lq_ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, dwbc_batch_link_query_bytes(b, what));
+    u.d = p;
+    return 1;
+}
+
+const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = link_query_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
 }
 
 }  // extern "C"

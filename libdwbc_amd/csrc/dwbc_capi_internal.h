@@ -120,6 +120,10 @@ struct dwbc_batch {
     bool upload_pending = false;
     int n_cu = 0;  // compute units of the batch's device
     bool tau_in_set = false;  // dwbc_batch_redistribute has a torque input: set through the mirror (created with the batch) or bound
+    // the link query (dwbc_batch_set_link_query): entries, whether Jacobians are written, and whether a launch has filled the outputs
+    int lq_n = 0, lq_link[16] = {};
+    double lq_point[16][3] = {};
+    bool lq_jac = false, lq_ran = false;
     dwbc::DumpLayout dl{};
 };
 

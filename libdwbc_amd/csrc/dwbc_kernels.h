@@ -11,6 +11,7 @@
 #include "dwbc_cycle2p.h"
 #include "dwbc_cycle_gc.h"
 #include "dwbc_redistribute.h"
+#include "dwbc_link_query.h"
 
 namespace dwbc {
 
@@ -96,6 +97,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
     redistribute_instance<N, NB, 64, Topo>(th, su, io, rio, inst, lds);
 }
 
+// link poses, velocities and Jacobians in a launch of their own (dwbc_link_query.h): forward kinematics and, for the COM link, the six
+// base rows of A -- 13 KB of LDS, no register cap; the tree is read at run time
+template <int N, int NB>
+__global__ __launch_bounds__(64) void dwbc_link_query_kernel(const BatchIO io, const LinkQueryIO lq) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    link_query_instance<N, NB, 64>(th, io, lq, inst, lds);
+}
+
 #define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
@@ -146,6 +158,12 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_REDIST(N, NB, TOPO, TK) \
     DWBC_ROW(N, NB, 0, TK, kRedist, 0u, (LdsRd<N, NB>::total_bytes), kNT, dwbc_redistribute_kernel, N, NB, dwbc::TOPO),
 #endif
+// the link-query kernel: fp64, any tree of its size (DWBC_NO_LINK_QUERY_KERNEL: fp32); not part of a kernel pack
+#ifdef DWBC_NO_LINK_QUERY_KERNEL
+#define DWBC_ROW_LINK_QUERY(N, NB)
+#else
+#define DWBC_ROW_LINK_QUERY(N, NB) DWBC_ROW(N, NB, 0, 0, kLinkQuery, 0u, (LdsLq<N, NB>::total_bytes), kNT, dwbc_link_query_kernel, N, NB),
+#endif
 // instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
 // and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
 // model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
@@ -166,6 +184,7 @@ const lp::Row kRows[] = {
 #endif
     DWBC_ROW_GC(39, 34, 6, 0u) DWBC_ROW_GC(39, 34, 12, lp::kWideTasks)
     DWBC_ROW_REDIST(39, 34, TopoTocabi, 1)
+    DWBC_ROW_LINK_QUERY(39, 34)
 };
 #endif
 

@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque or a link query):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -8,8 +8,9 @@
 namespace dwbc_plan {
 
 enum Arith { kDouble = 0, kFloat = 1 };
-// full-model cycle, reduced (centroidal) dynamics, general-contact cycle, redistribution of a caller-supplied torque (dwbc_redistribute.h)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3 };
+// full-model cycle, reduced (centroidal) dynamics, general-contact cycle, redistribution of a caller-supplied torque (dwbc_redistribute.h),
+// link poses / velocities / Jacobians on their own (dwbc_link_query.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -58,6 +59,9 @@ struct Request {
     // the batch carries per-instance torque limits and contact cone constants (BatchIO::inst_par): every kernel of the table reads them where
     // it fills a QP row, so no route changes; what has no QP rows to put them in is refused
     bool inst_par = false;
+    // not a cycle either: UpdateKinematics on its own for a set of queried links (dwbc_batch_update_kinematics); of the members above it reads
+    // the model and arith
+    bool link_query = false;
 };
 
 struct Plan {
@@ -111,6 +115,13 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         p.ws_valid_after = ws_valid_after;
         return p;
     };
+    // link query: one kernel for any tree of its size, whatever the batch size, the task set-up or the cycle's options are (it reads the state alone)
+    if (q.link_query) {
+        if (q.arith == kFloat) return refuse("link query: fp64 batches only");
+        const Row *r = Candidates(q, kLinkQuery, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no link-query kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
+        return run(r, false);
+    }
     // redistribution of a caller-supplied torque: one lean kernel, whatever the batch size or the task set-up (it runs no task level and
     // starts its one QP cold)
     if (q.redistribute) {
