@@ -85,6 +85,8 @@ def lib():
         L.orc_cycle_batch.restype = i32
         L.orc_solve_qp.argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_solve_qp.restype = i32
+        L.orc_solve_qp_tol.argtypes = L.orc_solve_qp.argtypes + [d]
+        L.orc_solve_qp_tol.restype = i32
         L.orc_pinv_cod.argtypes = [C.c_void_p, i32, i32, d, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_pinv_cod.restype = i32
         _lib = L
@@ -194,7 +196,8 @@ def cycle_batch(M, S, q, flags, fstar, nthreads=0):
     return tau, wr, st, used
 
 
-def solve_qp(A, ub, t, max_iter=1000):
+def solve_qp(A, ub, t, max_iter=1000, tol=None):
+    """tol: violation (slack / |row|) below which a row counts as satisfied during the search (orc_solve_qp_tol); None = QP_TOL"""
     L = lib()
     A = np.ascontiguousarray(A, dtype=np.float64)
     ub = np.ascontiguousarray(ub, dtype=np.float64)
@@ -203,7 +206,8 @@ def solve_qp(A, ub, t, max_iter=1000):
     act = np.zeros(MAXV, dtype=np.int32)
     nact = C.c_int(0)
     it = C.c_int(0)
-    st = L.orc_solve_qp(A.ctypes.data, ub.ctypes.data, rows, nv, t, max_iter, x.ctypes.data, act.ctypes.data, C.byref(nact), C.byref(it))
+    args = (A.ctypes.data, ub.ctypes.data, rows, nv, t, max_iter, x.ctypes.data, act.ctypes.data, C.byref(nact), C.byref(it))
+    st = L.orc_solve_qp(*args) if tol is None else L.orc_solve_qp_tol(*args, float(tol))
     return st, x, sorted(act[: nact.value].tolist()), it.value
 
 
