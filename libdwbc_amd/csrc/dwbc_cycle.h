@@ -1,6 +1,7 @@
 // dwbc_cycle.h -- helpers shared by the fused cycle kernels (dwbc_cycle2.h: full model, dwbc_reduced.h: reduced dynamics,
 // dwbc_nohqp.h, dwbc_hqp.h): synchronisation and stage-stamp macros, QP constants, small dense products on LDS operands, the
-// contact-cone rows, point Jacobians, the centroidal outputs and the assembly of the QP rows into lanes.
+// contact-cone rows, point Jacobians, the centroidal outputs and the assembly of the QP rows into lanes; and, through dwbc_front.h
+// (included at the end), the kinematics and CRBA front end.
 //
 // One workgroup (one 64-lane wavefront) owns ONE robot instance for the whole cycle; the kernels that include this keep every
 // intermediate in registers / LDS.  The helpers are NT-generic (strided loops, explicit synchronisation points) so that the SAME
@@ -545,3 +546,4 @@ DWBC_DEV void qp_rows_and_solve(const Setup &su, real_t *L, int nlim, int ncone,
 }
 
 }  // namespace dwbc
+#include "dwbc_front.h"  // kinematics and CRBA front end of every kernel (uses Thr and the macros above)

@@ -357,87 +357,18 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
         for (int i = th.tid; i < 3 * M; i += NT) L[S::tg + i] = real_t(0.0);
         DWBC_SYNC();
     }
-    constexpr int kPairRounds = (N * (N + 1) / 2 + NT - 1) / NT;
     const int npair = topo[3 * nb];
-    int pairw[kPairRounds];
-    if (is_main) {
-#pragma unroll
-        for (int r = 0; r < kPairRounds; r++) pairw[r] = (r * NT + th.tid < npair) ? topo[3 * nb + 1 + r * NT + th.tid] : 0;
-    }
+    int pairw[kCrbaPairRounds<N, NT>];
+    if (is_main) crba_pairs_fetch<N, NT>(th, topo, nb, npair, pairw);
     real_t *Rw = L + S::Rw, *pw = L + S::pw, *aw = L + S::aw, *Rl = L + S::k_Rl;
+    real_t *Iw = L + S::k_Iw, *Icm = L + S::k_Ic, *Sm = L + S::k_S, *Fm = L + S::k_F;
     if (is_main) {
-        const real_t *q = L + S::q;
-        for (int i = th.tid; i < nb; i += NT) {
-            const real_t *bd = body + i * kBodyStride;
-            if (i == 0) {
-                const real_t x = q[3], y = q[4], z = q[5], w = q[N];
-                real_t *R = Rw;
-                R[0] = 1 - 2 * y * y - 2 * z * z; R[1] = 2 * x * y - 2 * w * z; R[2] = 2 * x * z + 2 * w * y;
-                R[3] = 2 * x * y + 2 * w * z; R[4] = 1 - 2 * x * x - 2 * z * z; R[5] = 2 * y * z - 2 * w * x;
-                R[6] = 2 * x * z - 2 * w * y; R[7] = 2 * y * z + 2 * w * x; R[8] = 1 - 2 * x * x - 2 * y * y;
-                pw[0] = q[0]; pw[1] = q[1]; pw[2] = q[2];
-            } else {
-                const real_t ax = bd[BF_AXIS], ay = bd[BF_AXIS + 1], az = bd[BF_AXIS + 2];
-                real_t sn, cs;
-                sincos_r(q[6 + i - 1], &sn, &cs);
-                const real_t c1 = real_t(1.0) - cs;
-                real_t Rj[9];
-                Rj[0] = cs + ax * ax * c1; Rj[1] = ax * ay * c1 - az * sn; Rj[2] = ax * az * c1 + ay * sn;
-                Rj[3] = ay * ax * c1 + az * sn; Rj[4] = cs + ay * ay * c1; Rj[5] = ay * az * c1 - ax * sn;
-                Rj[6] = az * ax * c1 - ay * sn; Rj[7] = az * ay * c1 + ax * sn; Rj[8] = cs + az * az * c1;
-                for (int a = 0; a < 3; a++)
-                    for (int b = 0; b < 3; b++)
-                        Rl[i * 9 + a * 3 + b] = bd[BF_RT + a * 3] * Rj[b] + bd[BF_RT + a * 3 + 1] * Rj[3 + b] + bd[BF_RT + a * 3 + 2] * Rj[6 + b];
-            }
-        }
-        // world transforms by pointer jumping (dwbc_cycle2_stage0.inc)
-        {
-            constexpr int md = Topo::maxdepth;
-            int rounds = 0;
-            while ((1 << rounds) < md + 1) rounds++;
-            const bool odd = rounds & 1;
-            real_t *Rc_ = odd ? Rl : Rw, *Rn = odd ? Rw : Rl;
-            real_t *pc_ = odd ? L + S::k_Iw : pw, *pn = odd ? pw : L + S::k_Iw;
-            real_t *ac = L + S::k_anc, *an_ = L + S::k_anc + NB;
-            DWBC_SYNC();
-            for (int i = th.tid; i < nb; i += NT) {
-                const real_t *bd = body + i * kBodyStride;
-                real_t Ri[9], pi[3];
-                for (int a = 0; a < 9; a++) Ri[a] = (i == 0) ? Rw[a] : Rl[i * 9 + a];
-                for (int a = 0; a < 3; a++) pi[a] = (i == 0) ? pw[a] : bd[BF_PT + a];
-                const real_t an = (i == 0) ? -real_t(1.0) : (real_t)topo[i];
-                for (int a = 0; a < 9; a++) Rc_[i * 9 + a] = Ri[a];
-                for (int a = 0; a < 3; a++) pc_[i * 3 + a] = pi[a];
-                ac[i] = an;
-            }
-            for (int r = 0; r < rounds; r++) {
-                DWBC_SYNC();
-                for (int i = th.tid; i < nb; i += NT) {
-                    const int an = (int)ac[i];
-                    const int aa = an < 0 ? 0 : an;
-                    real_t Ri[9], pi[3], Ra[9], pa[3];
-                    for (int a = 0; a < 9; a++) { Ri[a] = Rc_[i * 9 + a]; Ra[a] = Rc_[aa * 9 + a]; }
-                    for (int a = 0; a < 3; a++) { pi[a] = pc_[i * 3 + a]; pa[a] = pc_[aa * 3 + a]; }
-                    const real_t a2 = ac[aa];
-                    real_t Ro[9], po[3];
-                    for (int a = 0; a < 3; a++) {
-                        for (int c = 0; c < 3; c++) Ro[a * 3 + c] = Ra[a * 3] * Ri[c] + Ra[a * 3 + 1] * Ri[3 + c] + Ra[a * 3 + 2] * Ri[6 + c];
-                        po[a] = pa[a] + Ra[a * 3] * pi[0] + Ra[a * 3 + 1] * pi[1] + Ra[a * 3 + 2] * pi[2];
-                    }
-                    for (int a = 0; a < 9; a++) Rn[i * 9 + a] = an < 0 ? Ri[a] : Ro[a];
-                    for (int a = 0; a < 3; a++) pn[i * 3 + a] = an < 0 ? pi[a] : po[a];
-                    an_[i] = an < 0 ? -real_t(1.0) : a2;
-                }
-                { real_t *t_ = Rc_; Rc_ = Rn; Rn = t_; t_ = pc_; pc_ = pn; pn = t_; t_ = ac; ac = an_; an_ = t_; }
-            }
-        }
+        joint_transforms<N, NT>(th, L + S::q, body, nb, Rw, pw, Rl);
+        // (second transform buffer: k_Rl and k_Iw; the ancestor table rides in k_Ic)
+        constexpr int kRounds = jump_rounds(Topo::maxdepth);
+        world_transforms_jump<NB, NT>(th, body, topo, nb, kRounds, Rw, pw, Rl, Iw, L + S::k_anc);
         DWBC_SYNC();
-        // world joint axes (the point Jacobians of the helper need them: before the barrier)
-        for (int i = th.tid; i < nb; i += NT) {
-            const real_t *bd = body + i * kBodyStride;
-            const real_t *R = Rw + i * 9;
-            for (int a = 0; a < 3; a++) aw[i * 3 + a] = R[a * 3] * bd[BF_AXIS] + R[a * 3 + 1] * bd[BF_AXIS + 1] + R[a * 3 + 2] * bd[BF_AXIS + 2];
-        }
+        world_axes<NT>(th, body, nb, Rw, aw);  // (the point Jacobians of the helper need them: before the barrier)
     }
     if (is_help) {
         // f* of every level (the lean build has no on-device task reference: the SetTaskSpace values)
@@ -449,135 +380,39 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
 
     // ================= phase 1 =================
     // world inertias and composite inertias: both waves (each forms the world inertias for itself -- identical values to identical
-    // places -- and takes five of the ten components through the prefix scan; the halves meet at B0a)
-    real_t *Iw = L + S::k_Iw, *Icm = L + S::k_Ic;
-    auto world_inertias = [&]() {
-        for (int i = th.tid; i < nb; i += NT) {
-            const real_t *bd = body + i * kBodyStride;
-            const real_t *R = Rw + i * 9;
-            const real_t m = bd[BF_MASS];
-            real_t r[3];
-            for (int a = 0; a < 3; a++)
-                r[a] = pw[i * 3 + a] + R[a * 3] * bd[BF_COM] + R[a * 3 + 1] * bd[BF_COM + 1] + R[a * 3 + 2] * bd[BF_COM + 2] - pw[a];
-            const real_t Ic[9] = {bd[BF_ICOM], bd[BF_ICOM + 1], bd[BF_ICOM + 2], bd[BF_ICOM + 1], bd[BF_ICOM + 3],
-                                  bd[BF_ICOM + 4], bd[BF_ICOM + 2], bd[BF_ICOM + 4], bd[BF_ICOM + 5]};
-            real_t Tm[9];
-            for (int a = 0; a < 3; a++)
-                for (int b = 0; b < 3; b++) Tm[a * 3 + b] = R[a * 3] * Ic[b] + R[a * 3 + 1] * Ic[3 + b] + R[a * 3 + 2] * Ic[6 + b];
-            const real_t rr2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-            real_t *o = Iw + i * 10;
-            o[0] = m;
-            o[1] = m * r[0]; o[2] = m * r[1]; o[3] = m * r[2];
-            int c = 4;
-            for (int a = 0; a < 3; a++)
-                for (int b = a; b < 3; b++) {
-                    real_t v = Tm[a * 3] * R[b * 3] + Tm[a * 3 + 1] * R[b * 3 + 1] + Tm[a * 3 + 2] * R[b * 3 + 2];
-                    v += m * ((a == b ? rr2 : real_t(0.0)) - r[a] * r[b]);
-                    o[c++] = v;
-                }
-        }
-        DWBC_SYNC();
-    };
-    auto composite_part = [&](auto c0c, auto c1c) {
-            // composite inertia of the subtree [b, b + len_b) (bodies are numbered depth first): inclusive prefix sums over the body order
-            // in registers (DPP), Ic[b] = P[b + len_b - 1] - P[b - 1].  Everything is expressed about the pelvis origin, where the smallest
-            // subtree (a wrist link, m r^2 ~ 0.1) is within 1e3 of the total: the difference keeps 13 digits.  (The window sums by doubling
-            // of the one-wave kernels -- six rounds through LDS -- were 7.3 k of this wave's 17 k cycles before the A^-1 sweep.)
-            constexpr int C0 = decltype(c0c)::value, C1 = decltype(c1c)::value, NCP = C1 - C0;
-            PLA(real_t, pf, NCP);
-            PL(int, len);
-            LANES {
-                const int bi = lane < nb ? lane : 0;
-                LV(len) = lane < nb ? topo[2 * nb + bi] : 1;
-#pragma unroll
-                for (int c = 0; c < NCP; c++) {
-                    const real_t v_ = Iw[bi * 10 + C0 + c];
-                    LV(pf)[c] = lane < nb ? v_ : real_t(0.0);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < NCP; c++) WAVE_PREFIX_A(pf, c);
-            LANES {
-                int e_ = lane + LV(len) - 1;
-                e_ = e_ < 63 ? e_ : 63;
-                const int s_ = lane > 0 ? lane - 1 : 0;
-#pragma unroll
-                for (int c = 0; c < NCP; c++) {
-                    const real_t hi_ = SHFLA(pf, c, e_), lo_ = SHFLA(pf, c, s_);
-                    if (lane < nb) Icm[lane * 10 + C0 + c] = hi_ - (lane > 0 ? lo_ : real_t(0.0));
-                }
-            }
-            DWBC_SYNC();
-    };
+    // places -- and takes five of the ten components through the prefix scan; the halves meet at B0a).  The window sums of the one-wave
+    // kernels (six rounds through LDS) were 7.3 k of this wave's 17 k cycles before the A^-1 sweep.
     if (is_main) {
-        world_inertias();
+        world_inertias<NT, false>(th, body, nb, Rw, pw, Iw);
+        DWBC_SYNC();
         DWBC_PSTAMP_M(51);  // world inertias
-        composite_part(std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
+        composite_inertias_scan<0, 5>(topo, nb, Iw, Icm);
+        DWBC_SYNC();
     }
     if (is_help) {
-        world_inertias();
-        composite_part(std::integral_constant<int, 5>{}, std::integral_constant<int, 10>{});
+        world_inertias<NT, false>(th, body, nb, Rw, pw, Iw);
+        DWBC_SYNC();
+        composite_inertias_scan<5, 10>(topo, nb, Iw, Icm);
+        DWBC_SYNC();
     }
-    real_t *Sm = L + S::k_S, *Fm = L + S::k_F;
     if (is_main) {
-        // motion axes S (frames only: before the halves meet), then F, CRBA, A -> registers, A^-1  (dwbc_cycle2_stage0.inc)
-        for (int j = th.tid; j < N; j += NT) {
-            real_t w[3] = {0, 0, 0}, v[3] = {0, 0, 0};
-            if (j < 3) {
-                v[j] = real_t(1.0);
-            } else if (j < 6) {
-                for (int a = 0; a < 3; a++) w[a] = Rw[a * 3 + (j - 3)];
-            } else {
-                const int b = j - 5;
-                for (int a = 0; a < 3; a++) w[a] = aw[b * 3 + a];
-                const real_t d0 = pw[b * 3] - pw[0], d1 = pw[b * 3 + 1] - pw[1], d2 = pw[b * 3 + 2] - pw[2];
-                v[0] = d1 * w[2] - d2 * w[1];
-                v[1] = d2 * w[0] - d0 * w[2];
-                v[2] = d0 * w[1] - d1 * w[0];
-            }
-            for (int a = 0; a < 3; a++) { Sm[j * 6 + a] = w[a]; Sm[j * 6 + 3 + a] = v[a]; }
-        }
+        // motion axes S (frames only: before the halves meet), then F, CRBA, A -> registers, A^-1
+        motion_axes<N, NT>(th, Rw, pw, aw, Sm);
         DWBC_SYNC();
     }
     DWBC_PAIR_BARRIER_X();  // ---- B0a: all ten components of the composite inertias
     if (is_main) {
         DWBC_PSTAMP_M(52);  // composite inertias, S
-        for (int j = th.tid; j < N; j += NT) {
-            const int b = j < 6 ? 0 : j - 5;
-            const real_t *I = Icm + b * 10;
-            const real_t *sv = Sm + j * 6;
-            const real_t m = I[0], h0 = I[1], h1 = I[2], h2 = I[3];
-            const real_t w0 = sv[0], w1 = sv[1], w2 = sv[2], v0 = sv[3], v1 = sv[4], v2 = sv[5];
-            Fm[j * 6 + 0] = I[4] * w0 + I[5] * w1 + I[6] * w2 + (h1 * v2 - h2 * v1);
-            Fm[j * 6 + 1] = I[5] * w0 + I[7] * w1 + I[8] * w2 + (h2 * v0 - h0 * v2);
-            Fm[j * 6 + 2] = I[6] * w0 + I[8] * w1 + I[9] * w2 + (h0 * v1 - h1 * v0);
-            Fm[j * 6 + 3] = m * v0 + (w1 * h2 - w2 * h1);
-            Fm[j * 6 + 4] = m * v1 + (w2 * h0 - w0 * h2);
-            Fm[j * 6 + 5] = m * v2 + (w0 * h1 - w1 * h0);
-        }
+        body_forces<N, NT>(th, Icm, Sm, Fm);
         DWBC_SYNC();
         DWBC_PSTAMP_M(53);  // forces F
         real_t *A = L + S::k_A;  // lower triangle, row-packed: (i, j <= i) at i (i + 1) / 2 + j
         for (int idx = th.tid; idx < N * (N + 1) / 2; idx += NT) A[idx] = real_t(0.0);
         DWBC_SYNC();
-#pragma unroll
-        for (int r = 0; r < kPairRounds; r++) {
-            if (r * NT + th.tid < npair) {
-                const int j = pairw[r] >> 8, kk = pairw[r] & 255;
-                const real_t *f = Fm + j * 6, *sv = Sm + kk * 6;
-                A[j * (j + 1) / 2 + kk] = sv[0] * f[0] + sv[1] * f[1] + sv[2] * f[2] + sv[3] * f[3] + sv[4] * f[4] + sv[5] * f[5];
-            }
-        }
+        crba_pairs_fill<N, NT>(th, npair, pairw, Sm, Fm, A);
         DWBC_SYNC();
         DWBC_PSTAMP_M(54);  // mass matrix pairs
-        LANES {
-            const int col = lane < N ? lane : 0;
-            const int cbase = col * (col + 1) / 2;
-#pragma unroll
-            for (int i = 0; i < N; i++) LV(s)[i] = (lane < N) ? A[i >= col ? i * (i + 1) / 2 + col : cbase + i] : real_t(0.0);
-            LV(dg) = (lane < N) ? A[cbase + col] : real_t(1.0);
-            if (lane < N) L[S::G + lane] = kGrav * A[col >= 2 ? cbase + 2 : 3 + col];  // G_ = 9.81 A[2,:] (dwbc.cpp:358)
-        }
+        load_mass_columns<N>(A, s, dg, L + S::G);
         DWBC_PSTAMP_M(41);  // CRBA done, columns of A in registers
     }
     if (is_help) {

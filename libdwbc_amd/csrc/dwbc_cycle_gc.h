@@ -389,140 +389,19 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
     DWBC_SYNC();
     {
         real_t *Rw = L + S::Rw, *pw = L + S::pw, *aw = L + S::aw, *Rl = L + S::k_Rl;
-        const real_t *q = L + S::q;
-        // local joint transforms R_T * Rot(axis, q_i)
-        for (int i = th.tid; i < nb; i += NT) {
-            const real_t *bd = body + i * kBodyStride;
-            if (i == 0) {
-                const real_t x = q[3], y = q[4], z = q[5], w = q[N];
-                real_t *R = Rw;
-                R[0] = 1 - 2 * y * y - 2 * z * z; R[1] = 2 * x * y - 2 * w * z; R[2] = 2 * x * z + 2 * w * y;
-                R[3] = 2 * x * y + 2 * w * z; R[4] = 1 - 2 * x * x - 2 * z * z; R[5] = 2 * y * z - 2 * w * x;
-                R[6] = 2 * x * z - 2 * w * y; R[7] = 2 * y * z + 2 * w * x; R[8] = 1 - 2 * x * x - 2 * y * y;
-                pw[0] = q[0]; pw[1] = q[1]; pw[2] = q[2];
-            } else {
-                const real_t ax = bd[BF_AXIS], ay = bd[BF_AXIS + 1], az = bd[BF_AXIS + 2];
-                real_t sn, cs;
-                sincos_r(q[6 + i - 1], &sn, &cs);
-                const real_t c1 = real_t(1.0) - cs;
-                real_t Rj[9];
-                Rj[0] = cs + ax * ax * c1; Rj[1] = ax * ay * c1 - az * sn; Rj[2] = ax * az * c1 + ay * sn;
-                Rj[3] = ay * ax * c1 + az * sn; Rj[4] = cs + ay * ay * c1; Rj[5] = ay * az * c1 - ax * sn;
-                Rj[6] = az * ax * c1 - ay * sn; Rj[7] = az * ay * c1 + ax * sn; Rj[8] = cs + az * az * c1;
-                for (int a = 0; a < 3; a++)
-                    for (int b = 0; b < 3; b++)
-                        Rl[i * 9 + a * 3 + b] = bd[BF_RT + a * 3] * Rj[b] + bd[BF_RT + a * 3 + 1] * Rj[3 + b] + bd[BF_RT + a * 3 + 2] * Rj[6 + b];
-            }
-        }
-        for (int d = 1; d <= su.maxdepth; d++) {
-            DWBC_SYNC();
-            for (int i = th.tid; i < nb; i += NT) {
-                if (topo[nb + i] != d) continue;
-                const int par = topo[i];
-                const real_t *bd = body + i * kBodyStride;
-                const real_t *Rp = Rw + par * 9;
-                for (int a = 0; a < 3; a++) {
-                    for (int b = 0; b < 3; b++)
-                        Rw[i * 9 + a * 3 + b] = Rp[a * 3] * Rl[i * 9 + b] + Rp[a * 3 + 1] * Rl[i * 9 + 3 + b] + Rp[a * 3 + 2] * Rl[i * 9 + 6 + b];
-                    pw[i * 3 + a] = pw[par * 3 + a] + Rp[a * 3] * bd[BF_PT] + Rp[a * 3 + 1] * bd[BF_PT + 1] + Rp[a * 3 + 2] * bd[BF_PT + 2];
-                }
-            }
-        }
+        real_t *Iw = L + S::k_Iw, *Icm = L + S::k_Ic, *Sm = L + S::k_S, *Fm = L + S::k_F;
+        joint_transforms<N, NT>(th, L + S::q, body, nb, Rw, pw, Rl);
+        world_transforms_depth<NT>(th, body, topo, nb, su.maxdepth, Rw, pw, Rl);
         DWBC_SYNC();
-        // world axes, world-frame spatial inertia of each body about O = pelvis origin
-        real_t *Iw = L + S::k_Iw;
-        for (int i = th.tid; i < nb; i += NT) {
-            const real_t *bd = body + i * kBodyStride;
-            const real_t *R = Rw + i * 9;
-            for (int a = 0; a < 3; a++) aw[i * 3 + a] = R[a * 3] * bd[BF_AXIS] + R[a * 3 + 1] * bd[BF_AXIS + 1] + R[a * 3 + 2] * bd[BF_AXIS + 2];
-            const real_t m = bd[BF_MASS];
-            real_t r[3];
-            for (int a = 0; a < 3; a++)
-                r[a] = pw[i * 3 + a] + R[a * 3] * bd[BF_COM] + R[a * 3 + 1] * bd[BF_COM + 1] + R[a * 3 + 2] * bd[BF_COM + 2] - pw[a];
-            const real_t Ic[9] = {bd[BF_ICOM], bd[BF_ICOM + 1], bd[BF_ICOM + 2], bd[BF_ICOM + 1], bd[BF_ICOM + 3],
-                                  bd[BF_ICOM + 4], bd[BF_ICOM + 2], bd[BF_ICOM + 4], bd[BF_ICOM + 5]};
-            real_t Tm[9];
-            for (int a = 0; a < 3; a++)
-                for (int b = 0; b < 3; b++) Tm[a * 3 + b] = R[a * 3] * Ic[b] + R[a * 3 + 1] * Ic[3 + b] + R[a * 3 + 2] * Ic[6 + b];
-            const real_t rr2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-            real_t *o = Iw + i * 10;
-            o[0] = m;
-            o[1] = m * r[0]; o[2] = m * r[1]; o[3] = m * r[2];
-            int c = 4;
-            for (int a = 0; a < 3; a++)
-                for (int b = a; b < 3; b++) {
-                    real_t v = Tm[a * 3] * R[b * 3] + Tm[a * 3 + 1] * R[b * 3 + 1] + Tm[a * 3 + 2] * R[b * 3 + 2];
-                    v += m * ((a == b ? rr2 : real_t(0.0)) - r[a] * r[b]);
-                    o[c++] = v;
-                }
-        }
+        world_inertias<NT, true>(th, body, nb, Rw, pw, Iw, aw);
         DWBC_SYNC();
-        // composite inertia: subtree of body i is the contiguous DFS range [i, i + subtree[i])
-        real_t *Icm = L + S::k_Ic;
-        {
-            // inclusive prefix sums over the body order in registers (DPP), Ic[b] = P[b + len_b - 1] - P[b - 1] (dwbc_cycle2p.h: everything is
-            // about the pelvis origin, where the smallest subtree is within 1e3 of the total) -- the sum over each subtree, one dependent
-            // LDS read per body of it, was 8 k cycles of this stage
-            static_assert(NB <= 64, "one body per lane");
-            DWBC_LANE_DECL;
-            PLA(real_t, pf, 10);
-            PL(int, len);
-            LANES {
-                const int bi = lane < nb ? lane : 0;
-                LV(len) = lane < nb ? topo[2 * nb + bi] : 1;
-#pragma unroll
-                for (int c = 0; c < 10; c++) {
-                    const real_t v_ = Iw[bi * 10 + c];
-                    LV(pf)[c] = lane < nb ? v_ : real_t(0.0);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 10; c++) WAVE_PREFIX_A(pf, c);
-            LANES {
-                int e_ = lane + LV(len) - 1;
-                e_ = e_ < 63 ? e_ : 63;
-                const int s_ = lane > 0 ? lane - 1 : 0;
-#pragma unroll
-                for (int c = 0; c < 10; c++) {
-                    const real_t hi_ = SHFLA(pf, c, e_), lo_ = SHFLA(pf, c, s_);
-                    if (lane < nb) Icm[lane * 10 + c] = hi_ - (lane > 0 ? lo_ : real_t(0.0));
-                }
-            }
-        }
-        // motion axes S_j = [omega; v_O] about O
-        real_t *Sm = L + S::k_S, *Fm = L + S::k_F;
-        for (int j = th.tid; j < N; j += NT) {
-            real_t w[3] = {0, 0, 0}, v[3] = {0, 0, 0};
-            if (j < 3) {
-                v[j] = real_t(1.0);
-            } else if (j < 6) {
-                for (int a = 0; a < 3; a++) w[a] = Rw[a * 3 + (j - 3)];
-            } else {
-                const int b = j - 5;
-                for (int a = 0; a < 3; a++) w[a] = aw[b * 3 + a];
-                const real_t d0 = pw[b * 3] - pw[0], d1 = pw[b * 3 + 1] - pw[1], d2 = pw[b * 3 + 2] - pw[2];
-                v[0] = d1 * w[2] - d2 * w[1];
-                v[1] = d2 * w[0] - d0 * w[2];
-                v[2] = d0 * w[1] - d1 * w[0];
-            }
-            for (int a = 0; a < 3; a++) { Sm[j * 6 + a] = w[a]; Sm[j * 6 + 3 + a] = v[a]; }
-        }
+        // (the sum over each subtree, one dependent LDS read per body of it, was 8 k cycles of this stage)
+        static_assert(NB <= 64, "one body per lane");
+        composite_inertias_scan<0, 10>(topo, nb, Iw, Icm);
+        motion_axes<N, NT>(th, Rw, pw, aw, Sm);
         for (int idx = th.tid; idx < N * N; idx += NT) L[S::bufA + idx] = real_t(0.0);
         DWBC_SYNC();
-        for (int j = th.tid; j < N; j += NT) {
-            const int b = j < 6 ? 0 : j - 5;
-            const real_t *I = Icm + b * 10;
-            const real_t *s = Sm + j * 6;
-            const real_t m = I[0], h0 = I[1], h1 = I[2], h2 = I[3];
-            const real_t w0 = s[0], w1 = s[1], w2 = s[2], v0 = s[3], v1 = s[4], v2 = s[5];
-            // L = I w + h x v ; p = m v + w x h
-            Fm[j * 6 + 0] = I[4] * w0 + I[5] * w1 + I[6] * w2 + (h1 * v2 - h2 * v1);
-            Fm[j * 6 + 1] = I[5] * w0 + I[7] * w1 + I[8] * w2 + (h2 * v0 - h0 * v2);
-            Fm[j * 6 + 2] = I[6] * w0 + I[8] * w1 + I[9] * w2 + (h0 * v1 - h1 * v0);
-            Fm[j * 6 + 3] = m * v0 + (w1 * h2 - w2 * h1);
-            Fm[j * 6 + 4] = m * v1 + (w2 * h0 - w0 * h2);
-            Fm[j * 6 + 5] = m * v2 + (w0 * h1 - w1 * h0);
-        }
+        body_forces<N, NT>(th, Icm, Sm, Fm);
         DWBC_SYNC();
         // A[j][k] = S_k . F_j for k on the path from j to the root (CRBA, [ext] RBDL CompositeRigidBodyAlgorithm)
         real_t *A = L + S::bufA;

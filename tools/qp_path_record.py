@@ -1,7 +1,8 @@
 """Is the path of the QP search the same in two builds of the library?  Records, for the bench's 1024 states and the tilted-feet and
 mixed-contact sets of tools/stress_parity.py, what every QP of every instance did -- steps (DG_QP_ITER), size of the final working set
 (DG_QP_NACT), on the full build the working set itself (DG_QP_ACT) -- and the outputs, through the two-wave kernel, the compact kernel
-and the full one-wave build; a second call compares two records bit for bit.
+and the full one-wave build, and the outputs of the general-contact kernel and the link query on the first 256 states of each set; a
+second call compares two records bit for bit.
     python tools/qp_path_record.py record OUT.npz          (DWBC_LIB_VARIANT selects the build, as everywhere)
     python tools/qp_path_record.py compare A.npz B.npz"""
 import os
@@ -46,7 +47,34 @@ def record(path):
                 out[key + "/act"] = d[:, 14:74]
             for f in ("tau", "wrench", "status"):
                 out[f"{key}/{f}"] = wbc.get(f)
+        record_others(D, W, sname, q, fs, out)
     np.savez(path, **out)
+
+
+def record_others(D, W, sname, q, fs, out, B=256):
+    """the kernels beside the cycle builds that share the front end (dwbc_front.h), at B = 256: the general-contact kernel with three flags
+    up and the link query (Jacobians, the COM link among the entries)"""
+    model = D.Model.from_urdf(W.URDF)
+    q, fs = q[:B], fs[:B]
+    wbc = D.Batch(model, B)
+    for c in W.CONTACTS_4:
+        wbc.add_contact(c["link"], c["point"], c["lx"], c["ly"], c["mu"], c["muz"])
+    wbc.add_task(0, D.TASK_LINK_6D, 0)
+    wbc.add_task(1, D.TASK_LINK_ROTATION, 15)
+    wbc.set_torque_limit(np.array(W.TAU_LIM))
+    wbc.set_max_active_contacts(3)
+    wbc.set_state(q); wbc.set_contact(np.tile(np.array([1, 1, 1, 0], np.uint8), (B, 1))); wbc.set_fstar_all(fs)
+    wbc.solve()
+    print(f"{sname + '/general_contact':24s} {wbc.kernel_name()[:70]:70s} ok {int(wbc.get('status').sum())}/{B}", flush=True)
+    for f in ("tau", "wrench", "status"):
+        out[f"{sname}/general_contact/{f}"] = wbc.get(f)
+    wbc = D.Batch(model, B)
+    wbc.set_state(q, np.random.default_rng(5).uniform(-1, 1, (B, 39)))
+    wbc.set_link_query([0, 6, 12, 15, 23, 33, model.link_id("COM")], None, jacobians=True)
+    wbc.update_kinematics()
+    print(f"{sname + '/link_query':24s} {wbc.link_query_kernel_name()[:70]}", flush=True)
+    for k, v in wbc.link_states().items():
+        out[f"{sname}/link_query/{k}"] = v
 
 
 def compare(pa, pb):
