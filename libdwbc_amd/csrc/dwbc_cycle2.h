@@ -372,8 +372,8 @@ DWBC_WDEV int sweep_inverse_tree(PLA_REF(real_t, s, NN), PL_REF(real_t, dg)) {
 // ds_read_b128 bring it back, two rows per instruction.  Issue cost per row update (tools/ubench/ubench3): 2 v_readlane + s_nop
 // + v_fma = 21 cycles against 8 (half a ds_read_b128) + 5.75; the compiler keeps only 2-3 such reads in flight, so all reads of
 // a column are issued back to back by hand and waited for once (profiles/r02_sweep_prototypes.txt: 24.9 k -> 16.3 k cycles).
-// The diagonal is carried shifted (dg - 2, next to the s[j][j] - 1 of the register sweep): with it the multiplier and the
-// diagonal update of the pivot lane are the same FMAs as every other lane's -- no per-pivot selects.
+// The diagonal is carried shifted (dg - 2, next to the s[j][j] - 1 of the register sweep): with it the multiplier of the pivot
+// lane is the same FMA as every other lane's; its new diagonal, -1/d, is the one per-pivot select (see lds_pivot).
 #if !defined(DWBC_HOST_EMU)
 typedef double dwbc_d2v __attribute__((ext_vector_type(2)));
 template <int P, int NP>
@@ -507,7 +507,10 @@ __device__ __forceinline__ void lds_pivot(double (&s)[NN], double &dg2, int &ok,
     lds_col_wait<NP>(col);
 #pragma unroll
     for (int i = 0; i < NN; i++) s[i] -= col[i / 2][i & 1] * h;
-    dg2 -= cj * h;              // pivot lane: (d - 2) - (d - 2 + 1/d) = -1/d
+    // pivot lane: -1/d.  Taken from rp, not from (d - 2) - (d - 1)^2 / d: that difference of two numbers of size d carries an error of
+    // u d on a result of size 1/d (tests/wave_cases.py, the synthetic tree matrix with pivots near 1e3: 6.7e4 u kappa off where the
+    // register sweep is 0.9 off)
+    dg2 = (lane == K + LO) ? -rp : dg2 - cj * h;
     if constexpr (K > 0) lds_pivot<NN, K - 1, LO>(s, dg2, ok, cb, lane);
 }
 #endif
@@ -567,7 +570,7 @@ __device__ __forceinline__ void lds_pivot_tree(double (&s)[NN], double &dg2, int
             if ((rel >> i) & 1ull) s[i] -= col[i / 2][i & 1] * h;
     }
     static_assert(3 * CHP >= NP, "at most three batches");
-    dg2 -= cj * h;
+    dg2 = (lane == K) ? -rp : dg2 - cj * h;  // (pivot lane: -1/d from rp, see lds_pivot)
     if constexpr (K > 0) lds_pivot_tree<Topo, NN, K - 1, CHP>(s, dg2, ok, cb, lane);
 }
 #endif
@@ -650,7 +653,7 @@ __device__ __forceinline__ void lds_step_tree(double (&s)[NN], double &dg2, int 
     constexpr int cnt = Sch::value.cnt[STEP];
     constexpr int NP = (NN + 1) / 2, CS = 2 * NP;  // column stride in LDS: the rows of the matrix only (lanes beyond carry right-hand sides)
     dwbc_d2v col[W][NP];
-    double cj[W], h[W];
+    double cj[W], h[W], nrp[W];
     const unsigned slot = cb + 8u * (unsigned)(lane < CS - 1 ? lane : CS - 1);  // (row CS - 1 is padding when NN is odd; lanes beyond write there)
     static_assert(NN % 2 == 1 || W == 1, "an even NN has no padding row for the lanes beyond the matrix");
     static_for<0, cnt>([&](auto qc) {
@@ -671,6 +674,7 @@ __device__ __forceinline__ void lds_step_tree(double (&s)[NN], double &dg2, int 
         const double rp = fast_rcp(d);
         cj[q] = s[K];
         h[q] = cj[q] * rp;
+        nrp[q] = -rp;
     });
     // the columns come back in the order they were asked for: the rows of pivot q are updated as soon as ITS pieces are in, while
     // the later columns are still on their way (the counter saturates at 15: a wait for more than that waits for 15)
@@ -683,7 +687,7 @@ __device__ __forceinline__ void lds_step_tree(double (&s)[NN], double &dg2, int 
 #pragma unroll
         for (int i = 0; i < NN; i++)
             if ((rel >> i) & 1ull) s[i] -= col[q][i / 2][i & 1] * h[q];
-        dg2 -= cj[q] * h[q];
+        dg2 = (lane == K) ? nrp[q] : dg2 - cj[q] * h[q];  // (pivot lane: -1/d from rp, see lds_pivot)
     });
     if constexpr (STEP + 1 < Sch::value.nsteps) lds_step_tree<Topo, NN, W, STEP + 1>(s, dg2, ok, cb, lane);
 }

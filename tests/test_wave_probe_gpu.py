@@ -1,0 +1,70 @@
+"""-m gpu: the wave-routine probe (tests/wave_probe) in its DEVICE build -- the bodies that ship behind the DWBC_HOST_EMU forks (DPP
+reductions and scans, v_readlane broadcasts, fast_rcp / fast_rsqrt / sincos_r, wave_gemm on the matrix cores, the LDS-fed sweeps,
+spd_inverse12_lds, the three-group Cholesky inverse, the hand-batched row products), each alone on the cases and against the 50-digit
+references of tests/wave_cases.py, with 64 and with 128 threads per block (the two-wave kernel runs them in wave 1).  One launch per
+instantiation.  The host twin, which validates the same cases and references, is tests/test_wave_probe_emu.py."""
+import pytest
+
+from tests import wave_cases as wc
+from tests.wave_probe import probe
+
+pytestmark = pytest.mark.gpu
+BUILD = "gpu"
+THREADS = pytest.mark.parametrize("threads", [64, 128])
+
+
+def test_instantiation_table_holds_every_family():
+    names = ["lanes", "lanes_f32", "math", "math_f32"] + [g[0] for g in wc.GEMM_INSTS] + list(wc.DOT_INSTS) + list(wc.AXPY_INSTS)
+    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS)
+    assert sorted(probe.table(BUILD)) == sorted(names)
+
+
+def test_entry_refuses_out_of_range_sizes():
+    wc.check_lanes_refusals(BUILD)
+
+
+@THREADS
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_cross_lane_primitives(f32, threads):
+    wc.check_lanes(BUILD, f32, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("op", [0, 1], ids=["fast_rcp", "fast_rsqrt"])
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_rcp_rsqrt(f32, op, threads):
+    wc.check_rcp_rsqrt(BUILD, f32, op, threads)
+
+
+@THREADS
+def test_sincos(threads):
+    wc.check_sincos(BUILD, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("inst", wc.GEMM_INSTS, ids=[g[0] for g in wc.GEMM_INSTS])
+def test_wave_gemm(inst, threads):
+    wc.check_gemm(BUILD, *inst, threads)
+
+
+@THREADS
+def test_wave_gemm_unit_matrices(threads):
+    wc.check_gemm_units(BUILD, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.DOT_INSTS))
+def test_lds_rows_dot(name, threads):
+    wc.check_rows_dot(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.AXPY_INSTS))
+def test_lds_rows_axpy(name, threads):
+    wc.check_rows_axpy(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS))
+def test_inverse(name, threads):
+    wc.check_inverse(BUILD, name, threads)

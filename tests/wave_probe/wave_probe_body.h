@@ -1,0 +1,401 @@
+// wave_probe_body.h -- TEST HARNESS ONLY.  Runs the shipped text of the device-only wave routines (libdwbc_amd/csrc/dwbc_wave.h,
+// dwbc_cycle2.h, dwbc_cycle2p.h) alone, on operands of the caller's choosing: one set of templates, compiled for the device
+// (wave_probe.hip -> libdwbc_wave_probe.so, one wavefront per problem, 64 or 128 threads per block -- the two-wave kernel runs these
+// routines in wave 1, where lane = threadIdx.x & 63) and for the host (the same files with DWBC_HOST_EMU -> libdwbc_wave_probe_emu.so).
+// The probe includes the shipped headers and calls the shipped functions; it holds no copy of any of them, and nothing of it is
+// linked into libdwbc_hip.so.  Included once per arithmetic type: wave_probe.hip (double, every family) and wave_probe_f32.hip
+// (WAVE_PROBE_F32: DWBC_REAL = float, namespace renamed; the cross-lane primitives and the scalar routines -- wave_gemm, the LDS-fed
+// sweeps and the batched row products are fp64-only on the device, their fp32 build takes the same plain code as the host).
+//
+// A family is a struct: NIN doubles and NIP ints in, NOUT doubles out per problem, LDS reals of scratch per wave (even: every wave's
+// slice and every operand in it starts at a 16-byte boundary, as the kernels place theirs), check(ip) for the run-time sizes and
+// problem(in, ip, out, L).  Outputs are the caller's, pre-filled with its sentinel: what a problem does not write keeps it.
+// Every loop of every routine under test has compile-time bounds; the probe's own copy loops run over compile-time counts.
+//
+// Rules the cross-lane arg-min relies on (read off the call sites: dwbc_qp_wave.h ratio test, dwbc_cycle_gc.h QR pivot):
+//   WAVE_ARGMIN / WAVE_ARGMIN_ROW1: every caller passes key = lane, i.e. keys INCREASE with the lane.  Under that contract the
+//     host rule (ties to the smaller key) and the device rule (ties to the smaller lane) agree; tests/wave_cases.py asserts it of its
+//     cases.  The device compares with the 7 lowest mantissa bits dropped: of two values that close either may win, and the value
+//     and key returned are the winner's own.  The device orders -0.0 below +0.0, the host does not: of zeros of mixed sign either
+//     lane may win (the callers form -fabs(x), all -0.0, or a step length that is equally valid at either lane).
+//   WAVE_ARGMIN_F32: first lane whose value, rounded to float, is the smallest.  The callers pass no NaN; when no lane compares
+//     equal to the minimum (all NaN) both builds return lane 0.  With NaN in SOME lanes the builds differ (fminf skips a NaN, the
+//     host's `<` never leaves a NaN in lane 0): not relied on, not tested.
+#pragma once
+#include <limits>
+
+#ifdef WAVE_PROBE_F32
+#include "../../libdwbc_amd/csrc/dwbc_cycle.h"
+#else
+#include "../../libdwbc_amd/csrc/dwbc_cycle_gc.h"
+#endif
+
+namespace dwbc {
+
+struct WpArgs {
+    int B;
+    const double *in;
+    const int *ip;
+    double *out;
+};
+
+constexpr double kWpSentinel = -7777.0;
+constexpr int wp_ev(int x) { return (x + 1) & ~1; }
+#define WP_NAN std::numeric_limits<real_t>::quiet_NaN()
+
+// ---- 1. cross-lane primitives.  in: val[64] key[64] src[64] flag[64]; ip: the uniform source lane.
+// out: 0 sum, 1 any, 2/3 arg-min value/key, 4/5 the same over lanes 16..31, 6 WAVE_ARGMIN_F32's lane, 7 BCAST, 8 BCASTA, 9 BCASTI;
+// 16.. WAVE_PREFIX_A of element 1, 80.. SHFL, 144.. SHFLA (per-lane source), 208.. element 0 of the prefix array (must stay -1)
+struct WpLanes {
+    static constexpr int NIN = 256, NIP = 1, NOUT = 272, LDS = 2;
+    static const char *check(const int *ip) { return (ip[0] < 0 || ip[0] > 63) ? "source lane outside 0..63" : nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *) {
+        DWBC_LANE_DECL;
+        PL(real_t, val);
+        PL(int, key);
+        PL(int, src);
+        PL(int, flag);
+        PLA(real_t, arr, 2);
+        PL(real_t, sh);
+        PL(real_t, sha);
+#ifdef DWBC_HOST_EMU
+        const int usrc = ip[0];
+#else
+        const int usrc = __builtin_amdgcn_readfirstlane(ip[0]);
+#endif
+        LANES {
+            const double v = in[lane];
+            LV(val) = v >= (double)DWBC_QP_INF ? DWBC_QP_INF : (real_t)v;
+            LV(key) = (int)in[64 + lane];
+            LV(src) = (int)in[128 + lane] & 63;
+            LV(flag) = in[192 + lane] != 0.0 ? 1 : 0;
+            LV(arr)[0] = real_t(-1.0);
+            LV(arr)[1] = LV(val);
+        }
+        real_t sum, av, rv;
+        int ak, rk, fl;
+        bool any;
+        WAVE_SUM(val, sum);
+        WAVE_ANY(flag, any);
+        WAVE_ARGMIN(val, key, av, ak);
+        WAVE_ARGMIN_ROW1(val, key, rv, rk);
+        WAVE_ARGMIN_F32(val, fl);
+        const real_t bc = BCAST(val, usrc), bca = BCASTA(arr, 1, usrc);
+        const int bci = BCASTI(key, usrc);
+        LANES {
+            LV(sh) = SHFL(val, LV(src));
+            LV(sha) = SHFLA(arr, 1, LV(src));
+        }
+        WAVE_PREFIX_A(arr, 1);
+        LANES {
+            if (lane == 0) {
+                out[0] = (double)sum, out[1] = any ? 1.0 : 0.0, out[2] = (double)av, out[3] = ak, out[4] = (double)rv, out[5] = rk;
+                out[6] = fl, out[7] = (double)bc, out[8] = (double)bca, out[9] = bci;
+            }
+            out[16 + lane] = (double)LV(arr)[1];
+            out[80 + lane] = (double)LV(sh);
+            out[144 + lane] = (double)LV(sha);
+            out[208 + lane] = (double)LV(arr)[0];
+        }
+    }
+};
+
+// ---- 2. scalar math, one argument per lane.  ip: 0 fast_rcp, 1 fast_rsqrt, 2 sincos_r.  out: result[64], second result[64] (cos)
+struct WpMath {
+    static constexpr int NIN = 64, NIP = 1, NOUT = 128, LDS = 2;
+    static const char *check(const int *ip) { return (ip[0] < 0 || ip[0] > 2) ? "operation outside 0..2" : nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *) {
+        DWBC_LANE_DECL;
+        const int op = ip[0];
+        LANES {
+            const real_t x = (real_t)in[lane];
+            real_t a = real_t(0.0), b = real_t(0.0);
+            if (op == 0) a = fast_rcp(x);
+            else if (op == 1) a = fast_rsqrt(x);
+            else sincos_r(x, &a, &b);
+            out[lane] = (double)a;
+            out[64 + lane] = (double)b;
+        }
+    }
+};
+
+#ifndef WAVE_PROBE_F32
+// (range clamp of an address only: the index the accessor was CALLED with is noted unclamped and asserted by the tests)
+DWBC_WDEV int wp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- 3. wave_gemm.  in: A (MR x KV), B (KV x NCV), C0 (MR x NCV), row-major.  In LDS each sits inside a frame of NaN (one guard
+// row / column on every side); the result goes to a framed block pre-filled with the sentinel -- or, OVER (with SYNC_STORE), over
+// the leading NCV columns of A.  out: that whole framed block, then per lane the smallest (3) and largest (3) row, reduction and
+// column index any accessor was called with.
+template <int MR, int NCV, int KV, bool FC, bool OVER>
+struct WpGemm {
+    static constexpr int AC = KV + 2, BC = NCV + 2, CC = NCV + 2;
+    static constexpr int oA = 0, oB = oA + wp_ev((MR + 2) * AC), oC = oB + wp_ev((KV + 2) * BC), oD = oC + wp_ev((MR + 2) * CC);
+    static constexpr int LDS = oD + wp_ev((MR + 2) * CC);
+    static constexpr int NF = OVER ? (MR + 2) * AC : (MR + 2) * CC;
+    static constexpr int NIN = MR * KV + KV * NCV + MR * NCV, NIP = 1, NOUT = NF + 64 * 6;
+    static_assert(oB % 2 == 0 && oC % 2 == 0 && oD % 2 == 0 && LDS % 2 == 0, "16-byte aligned operands");
+    static_assert(!OVER || NCV <= KV, "the result fits over A");
+    static const char *check(const int *) { return nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        real_t *Af = L + oA, *Bf = L + oB, *Cf = L + oC, *Df = L + oD;
+        LANES {
+            for (int x = lane; x < LDS; x += 64) L[x] = (x >= oD && x < oD + (MR + 2) * CC) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int x = lane; x < MR * KV; x += 64) Af[(x / KV + 1) * AC + x % KV + 1] = (real_t)in[x];
+            for (int x = lane; x < KV * NCV; x += 64) Bf[(x / NCV + 1) * BC + x % NCV + 1] = (real_t)in[MR * KV + x];
+            for (int x = lane; x < MR * NCV; x += 64) Cf[(x / NCV + 1) * CC + x % NCV + 1] = (real_t)in[MR * KV + KV * NCV + x];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-(1 << 30), -(1 << 30), -(1 << 30)};
+        auto note = [&](int d, int v) {
+            lo[d] = v < lo[d] ? v : lo[d];
+            hi[d] = v > hi[d] ? v : hi[d];
+        };
+        auto fa = [&](auto, auto, int i, int k) {
+            note(0, i), note(1, k);
+            return Af[(wp_clampi(i, -1, MR) + 1) * AC + wp_clampi(k, -1, KV) + 1];
+        };
+        auto fb = [&](auto, int k, int j) {
+            note(1, k), note(2, j);
+            return Bf[(wp_clampi(k, -1, KV) + 1) * BC + wp_clampi(j, -1, NCV) + 1];
+        };
+        auto fc = [&](int i, int j) {
+            note(0, i), note(2, j);
+            return Cf[(wp_clampi(i, -1, MR) + 1) * CC + wp_clampi(j, -1, NCV) + 1];
+        };
+        auto fs = [&](int i, int j, real_t v) {
+            note(0, i), note(2, j);
+            const int ci = wp_clampi(i, -1, MR) + 1, cj = wp_clampi(j, -1, NCV) + 1;
+            if (OVER) Af[ci * AC + cj] = v; else Df[ci * CC + cj] = v;
+        };
+        if constexpr (FC) wave_gemm<MR, NCV, KV, OVER>(fa, fb, fs, fc);
+        else wave_gemm<MR, NCV, KV, OVER>(fa, fb, fs);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            const real_t *F = OVER ? Af : Df;
+            for (int x = lane; x < NF; x += 64) out[x] = (double)F[x];
+            for (int d = 0; d < 3; d++) out[NF + lane * 6 + d] = lo[d], out[NF + lane * 6 + 3 + d] = hi[d];
+        }
+    }
+};
+
+// ---- 5. lds_rows_dot / lds_rows_axpy.  The matrix sits at a 16-byte aligned offset inside NaN: two reals before it, its padding
+// columns NC .. RS-1, and everything behind its last row (the element just past it included).
+// dot: in A (NR x NC), x (64 x NC: the lane's register column), out0 (64 x NO: what `out` holds before);  out: 64 x NO
+template <int NR, int NC, int RS, int CH, int MODE, bool AL, int OFF, int NO>
+struct WpRowsDot {
+    static constexpr int oA = 2, LDS = oA + wp_ev(NR * RS) + 4;
+    static constexpr int NIN = NR * NC + 64 * NC + 64 * NO, NIP = 1, NOUT = 64 * NO;
+    static_assert(oA % 2 == 0 && LDS % 2 == 0, "16-byte aligned matrix");
+    static const char *check(const int *) { return nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        PLA(real_t, x, NC);
+        PLA(real_t, o, NO);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < NR * NC; e += 64) L[oA + (e / NC) * RS + e % NC] = (real_t)in[e];
+#pragma unroll
+            for (int i = 0; i < NC; i++) LV(x)[i] = (real_t)in[NR * NC + lane * NC + i];
+#pragma unroll
+            for (int i = 0; i < NO; i++) LV(o)[i] = (real_t)in[NR * NC + 64 * NC + lane * NO + i];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        LANES { lds_rows_dot<NR, NC, RS, CH, MODE, AL, OFF, NO>(L + oA, LV(x), LV(o)); }
+        LANES {
+#pragma unroll
+            for (int i = 0; i < NO; i++) out[lane * NO + i] = (double)LV(o)[i];
+        }
+    }
+};
+// axpy: in A (NR x NC), x (64 x NR), acc0 (64 x NC);  out: 64 x NC
+template <int NR, int NC, int RS, int CH, bool AL>
+struct WpRowsAxpy {
+    static constexpr int oA = 2, LDS = oA + wp_ev(NR * RS) + 4;
+    static constexpr int NIN = NR * NC + 64 * NR + 64 * NC, NIP = 1, NOUT = 64 * NC;
+    static_assert(oA % 2 == 0 && LDS % 2 == 0, "16-byte aligned matrix");
+    static const char *check(const int *) { return nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        PLA(real_t, x, NR);
+        PLA(real_t, o, NC);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < NR * NC; e += 64) L[oA + (e / NC) * RS + e % NC] = (real_t)in[e];
+#pragma unroll
+            for (int i = 0; i < NR; i++) LV(x)[i] = (real_t)in[NR * NC + lane * NR + i];
+#pragma unroll
+            for (int i = 0; i < NC; i++) LV(o)[i] = (real_t)in[NR * NC + 64 * NR + lane * NC + i];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        LANES { lds_rows_axpy<NR, NC, RS, CH, AL>(L + oA, LV(x), LV(o)); }
+        LANES {
+#pragma unroll
+            for (int i = 0; i < NC; i++) out[lane * NC + i] = (double)LV(o)[i];
+        }
+    }
+};
+
+// ---- 4. inverses.
+// The register / LDS-fed sweeps on a column-per-lane matrix.  KIND 0: sweep_inverse_tree<TopoTocabi, 39>, 1: sweep_inverse_tree_lds,
+// 2: sweep_inverse_tree_lds_multi<.., DWBC_SWEEP_W>, 3: sweep_inverse_tree<TopoDense<33>, 33>, 4: sweep_inverse_lds<33>.
+// in: 64 x NN, the register column of every lane: lanes < NN a column of the matrix (its diagonal goes to dg), lanes >= NN a
+// right-hand side riding along with dg = 1, as the two-wave cycle loads them (dwbc_cycle2p.h, phase 1b).
+// out: the 64 columns after the sweep, dg[64], ok
+#ifndef DWBC_SWEEP_W
+#define DWBC_SWEEP_W 4
+#endif
+template <int KIND>
+struct WpSweep {
+    static constexpr int NN = KIND < 3 ? 39 : 33;
+    static constexpr int LDS = DWBC_SWEEP_W * 2 * ((NN + 1) / 2) + 2;  // (>= 64: the single-pivot sweeps give every lane a slot)
+    static constexpr int NIN = 64 * NN, NIP = 1, NOUT = 64 * NN + 64 + 1;
+    static_assert(LDS >= 66 && LDS % 2 == 0, "column buffer");
+    static const char *check(const int *) { return nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        PLA(real_t, s, NN);
+        PL(real_t, dg);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = WP_NAN;
+#pragma unroll
+            for (int i = 0; i < NN; i++) LV(s)[i] = (real_t)in[lane * NN + i];
+            LV(dg) = lane < NN ? (real_t)in[lane * NN + (lane < NN ? lane : 0)] : real_t(1.0);
+        }
+        WSYNC();
+        DWBC_SYNC();
+        int ok;
+        if constexpr (KIND == 0) ok = sweep_inverse_tree<TopoTocabi, 39>(s, dg);
+        else if constexpr (KIND == 1) ok = sweep_inverse_tree_lds<TopoTocabi, 39>(s, dg, L);
+        else if constexpr (KIND == 2) ok = sweep_inverse_tree_lds_multi<TopoTocabi, 39, DWBC_SWEEP_W>(s, dg, L);
+        else if constexpr (KIND == 3) ok = sweep_inverse_tree<TopoDense<33>, 33>(s, dg);
+        else ok = sweep_inverse_lds<33>(s, dg, L);
+        DWBC_SYNC();
+        LANES {
+#pragma unroll
+            for (int i = 0; i < NN; i++) out[lane * NN + i] = (double)LV(s)[i];
+            out[64 * NN + lane] = (double)LV(dg);
+            if (lane == 0) out[64 * NN + 64] = ok;
+        }
+    }
+};
+
+// The LDS-resident small inverses.  KIND 0: spd_inverse_small (ip: n = 1..12, row stride 12 -- n < 12 leaves pivots out of the
+// 12-wide sweep, n <= 6 goes to the Cholesky form), 1: spd_inverse12_lds out of place, 2: the same with Out == Mx,
+// 3: spd_inverse_chol6 (ip: n = 1..6, row stride 6, with the pivot ratio).  in: 12 x 12 (KIND 3: 6 x 6).
+// out: the output block (pre-filled with the sentinel where it is not the input), ok, pivot ratio
+template <int KIND>
+struct WpSmall {
+    static constexpr int LD = KIND == 3 ? 6 : 12;
+    static constexpr int oM = 0, oO = 144, oS = 288, LDS = 288 + 12 + 2;
+    static constexpr int NIN = LD * LD, NIP = 1, NOUT = LD * LD + 2;
+    static const char *check(const int *ip) {
+        if (KIND == 0 && (ip[0] < 1 || ip[0] > 12)) return "n outside 1..12";
+        if (KIND == 3 && (ip[0] < 1 || ip[0] > 6)) return "n outside 1..6";
+        return nullptr;
+    }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int n = ip[0];
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= oO && e < oO + 144) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < LD * LD; e += 64) L[oM + e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        real_t *Mx = L + oM, *Out = KIND == 2 ? L + oM : L + oO;
+        real_t pr = real_t(-1.0);
+        int ok;
+        if constexpr (KIND == 0) ok = spd_inverse_small(Mx, 12, n, Out, 12, L + oS);
+        else if constexpr (KIND == 3) ok = spd_inverse_chol6(Mx, 6, n, Out, 6, &pr);
+        else ok = spd_inverse12_lds(Mx, Out, L + oS);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < LD * LD; e += 64) out[e] = (double)Out[e];
+            if (lane == 0) out[LD * LD] = ok, out[LD * LD + 1] = (double)pr;
+        }
+    }
+};
+
+// spd_inverse_chol6_x3 as the helper wave calls it: three densely stored matrices (row stride n_q; ip: n0 n1 n2, each 0..6), the first
+// two out of place, the third in place.  in: 3 x 36;  out: 3 x 36 (the three output blocks), ok[3]
+struct WpChol3 {
+    static constexpr int LDS = 5 * 36 + 2;
+    static constexpr int NIN = 108, NIP = 3, NOUT = 111;
+    static const char *check(const int *ip) {
+        for (int q = 0; q < 3; q++)
+            if (ip[q] < 0 || ip[q] > 6) return "n outside 0..6";
+        return nullptr;
+    }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= 108 && e < 180) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 108; e += 64) L[e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        int ok3[3] = {-1, -1, -1};
+        spd_inverse_chol6_x3(L, ip[0], L + 108, L + 36, ip[1], L + 144, L + 72, ip[2], L + 72, ok3);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 72; e += 64) out[e] = (double)L[108 + e];
+            for (int e = lane; e < 36; e += 64) out[72 + e] = (double)L[72 + e];
+            if (lane == 0) out[108] = ok3[0], out[109] = ok3[1], out[110] = ok3[2];
+        }
+    }
+};
+#endif  // !WAVE_PROBE_F32
+
+#ifndef DWBC_HOST_EMU
+template <class F>
+__global__ __launch_bounds__(128) void wp_kernel(const WpArgs a) {
+    __shared__ __attribute__((aligned(16))) real_t Ls[2 * F::LDS];
+    static_assert(F::LDS % 2 == 0 && 2 * F::LDS * sizeof(real_t) <= 60000, "wave slices of LDS");
+    const int wave = (int)(threadIdx.x >> 6);
+    const int b = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
+    if (b >= a.B) return;  // (the whole wave: the routines hold no block-wide barrier)
+    F::problem(a.in + (size_t)b * F::NIN, a.ip + (size_t)b * F::NIP, a.out + (size_t)b * F::NOUT, Ls + wave * F::LDS);
+}
+#endif
+
+// runs the batch; nullptr or the error text.  The caller (wave_probe.hip) has checked every size; on the device `a` holds device pointers
+template <class F>
+static const char *wp_run(const WpArgs &a, int threads) {
+#ifdef DWBC_HOST_EMU
+    (void)threads;
+    static real_t L[F::LDS];
+    for (int b = 0; b < a.B; b++) F::problem(a.in + (size_t)b * F::NIN, a.ip + (size_t)b * F::NIP, a.out + (size_t)b * F::NOUT, L);
+    return nullptr;
+#else
+    const int per = threads / 64;
+    hipLaunchKernelGGL((wp_kernel<F>), dim3((a.B + per - 1) / per), dim3(threads), 0, 0, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+#endif
+}
+
+}  // namespace dwbc
