@@ -273,7 +273,7 @@ const char *dwbc_batch_kernel_name(const dwbc_batch *b);
  * Per instance: one active contact -> zero torque, status 1 (the wrenches are still evaluated); none -> zeros, status 1; more than two
  * flags raised, a failed contact stage or a failed QP -> status 0, zero torque.
  * Refused (dwbc_last_error): DWBC_F32 batches, dwbc_batch_set_max_active_contacts(b, 3), a model without the kernel (built in for
- * TOCABI's size and tree), DWBC_SOLVE_HQP clear (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque), and a
+ * TOCABI's size on its own tree and on any; every kernel pack carries its size's), DWBC_SOLVE_HQP clear (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque), and a
  * torque input that was never set.  DWBC_SOLVE_INIT clear is accepted and runs cold: the QP is strictly convex, its point does not
  * depend on the start. */
 int dwbc_batch_set_torque_input(dwbc_batch *b, const double *tau);   /* B x m; the mirror of dwbc_batch_host_ptr(b, DWBC_IN_TORQUE) is taken in place */

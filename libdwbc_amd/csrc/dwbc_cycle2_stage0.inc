@@ -269,7 +269,15 @@
         // beyond 40 columns the runtime-pivot sweep would pick the lane's own pivot-row element from six candidate registers, which
         // the compiler turns into ONE load through a selected address -- and the whole column array then lives in scratch (4 x
         // slower at 43 dof).  Compile-time pivots (the dense "tree") keep every index static.
-        if constexpr (N > 40) {
+        // compact lean build (the redistribution kernel on any tree): leaves-first pivots fed through LDS, the dense form of the sweep the
+        // constant-tree build of that kernel runs.  In this order the entries outside a tree's pattern stay exact zeros, so on a model
+        // whose tree the constant-tree build knows the two builds compute the same A^-1 to the bit, where the ascending runtime pivots
+        // below eliminate in another order (1e-16 apart in A^-1, which an ill-conditioned redistribution QP shows as 5e-9 Nm)
+        if constexpr (S::compact && !kExtras && sizeof(real_t) == 8) {
+            DWBC_SYNC();
+            if (!sweep_inverse_tree_lds<TopoDense<N>, N>(s, dg, L + S::c_s1)) st_contact = 0;
+            DWBC_SYNC();
+        } else if constexpr (N > 40) {
             if (!sweep_inverse_tree<TopoDense<N>, N>(s, dg)) st_contact = 0;
         } else {
             if (!sweep_inverse_rl<N>(s, dg)) st_contact = 0;

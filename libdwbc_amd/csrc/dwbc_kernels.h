@@ -87,7 +87,8 @@ __global__ __launch_bounds__(NT) void dwbc_cycle_kernel_reduced(const Setup su, 
 }
 
 // contact redistribution of a caller-supplied torque (dwbc_redistribute.h): the front half of the cycle and one six-variable QP on the
-// compact map's footprint -- register-capped like `_v2`, eight workgroups per CU
+// compact map's footprint (LdsRd: 12.9 KB at 23 dof, 20.4 KB at 39, 26.8 KB at 50) -- register-capped like `_v2`, up to eight workgroups
+// per CU; no instantiation spills to scratch under the cap, the 43-dof TopoDense route included, so there is no uncapped variant
 template <int N, int NB, class Topo>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_redistribute_kernel(const Setup su, const BatchIO io, const RedistIO rio) {
     extern __shared__ __attribute__((aligned(16))) real_t lds[];
@@ -151,7 +152,7 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_PAIR(NLV) \
     DWBC_ROW(39, 34, NLV, 1, kCycle, lp::kLean | lp::kTwoWave, (Lds4<39, 34, NLV>::total_bytes), 2 * kNT, dwbc_cycle_kernel_v2p, 39, 34, NLV, dwbc::TopoTocabi),
 #endif
-// the redistribution kernel: fp64, TOCABI's constant tree (DWBC_NO_REDIST_KERNEL: fp32); not part of a kernel pack
+// the redistribution kernel: fp64 (DWBC_NO_REDIST_KERNEL: fp32), for a constant tree or any tree of the size; every kernel pack carries its own
 #ifdef DWBC_NO_REDIST_KERNEL
 #define DWBC_ROW_REDIST(N, NB, TOPO, TK)
 #else
@@ -183,7 +184,7 @@ const lp::Row kRows[] = {
     DWBC_ROWS_TOCABI_ANY(1) DWBC_ROWS_TOCABI_ANY(2) DWBC_ROWS_TOCABI_ANY(3) DWBC_ROWS_TOCABI_ANY(4)
 #endif
     DWBC_ROW_GC(39, 34, 6, 0u) DWBC_ROW_GC(39, 34, 12, lp::kWideTasks)
-    DWBC_ROW_REDIST(39, 34, TopoTocabi, 1)
+    DWBC_ROW_REDIST(39, 34, TopoTocabi, 1) DWBC_ROW_REDIST(39, 34, TopoGeneric, 0)
     DWBC_ROW_LINK_QUERY(39, 34)
 };
 #endif

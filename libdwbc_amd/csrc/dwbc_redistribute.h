@@ -26,8 +26,8 @@ struct RedistIO {
     int *status;         // B       1 ok / 0 failed
 };
 
-// LDS map: the compact map's stage-0 / stage-1 / NwJw placement (Lds3 at one task level, dwbc_cycle2.h) -- those stages are the same
-// text -- with the blocks behind them named for what this kernel keeps there.  Life times (region : stage 0 | stage 1 | NwJw | maps + QP):
+// LDS map: the order of the compact map's stage-0 / stage-1 / NwJw blocks (Lds3 at one task level, dwbc_cycle2.h) -- those stages are
+// the same text -- with the blocks behind them named for what this kernel keeps there.  Life times (region : stage 0 | stage 1 | NwJw | maps + QP):
 //   head : q, G ............. G (P_C) | .    | .
 //   JbT  : k_S k_F          | J_C, then Jbar^T .......................... (maps, wrench outputs)
 //   NwJw : .                | .              | NwJw .................... (QP rows, torque output)
@@ -36,17 +36,101 @@ struct RedistIO {
 //   RF   : k_Iw k_Ic (k_Rl, k_A over them) | Vb ........... | (QP scratch reaches into it)
 //   RG   : (k_Ic, k_A)      | Y              | .    | .
 //   RX   : (k_A), sweep column | Lambda_c, small-inverse scratch ... | FN (unrotated maps, kept for the wrench outputs)
-// The size is set by stage 0: the row-packed mass matrix (N (N + 1) / 2 doubles) staged beside S, F, the link frames and the state.
-// TOCABI: 20 432 B, eight workgroups per CU.
+// The map is laid out for every model size a kernel runs at (N = NB + 5 <= 50), not for TOCABI's alone.  Lds3 sizes its regions for the
+// tenants of the CYCLE, and three of its borrowings do not carry over: the QP scratch outgrows RE .. RG below 39 dof (RE .. RG shrinks
+// with M, the C x WLD wrench maps do not), Y fills RG .. RX to the last double at every even N, and the packed mass matrix runs past
+// the end of the map from 46 dof on.  So every region here is as large as the largest of ITS tenants: U holds the link rotations or
+// 2 M T, the QP scratch may run on through RG (Y is dead by then) and pushes RX back where it would reach FN, and the map ends behind
+// the last of the small-inverse block, the staged mass matrix and the composite inertias.  The blocks this kernel never writes (FNl, the
+// task points, G^-1) keep their places, so that at 39 / 34 every offset is the compact map's and TOCABI's kernel is the one it was
+// (asserted below the struct).
+// Bytes (N / NB: total_bytes, workgroups that fit a CU's 160 KB):  23 / 18: 12 880, 12    37 / 32: 19 488, 8    39 / 34: 20 432, 8
+//                                                                  43 / 38: 22 320, 7     50 / 45: 26 792, 6
+// (the register cap of two waves per SIMD allows eight one-wave workgroups per CU whatever the map says)
 template <int N, int NB>
-struct LdsRd : Lds3<N, NB, 1> {
-    using Base = Lds3<N, NB, 1>;
-    static constexpr int FLD = 8;                // row stride of FN: 1 + K columns, padded to an even number
-    static constexpr int t_in = Base::t_base;    // M: tau_in (the `base` of the QP's torque rows)
-    static constexpr int fn = Base::c_s2;        // C x FLD: Jbar[:, 6:] [tau_in | NwJw], world frame
-    static_assert(Base::C * FLD <= Base::C * Base::C, "FN borrows the input block of the small inverses");
-    static_assert(1 + Base::K <= FLD && 1 + Base::K <= Base::WLD, "columns of the wrench maps");
+struct LdsRd {
+    static constexpr bool compact = true;
+    static constexpr int M = N - 6;
+    static constexpr int C = 6 * kMaxActiveContacts;
+    static constexpr int K = C - 6;
+    static constexpr int T = kMaxTaskDof;
+    static constexpr int max2(int a, int b) { return a > b ? a : b; }
+    static constexpr int ev(int a) { return (a + 1) & ~1; }
+    // ---- head: the stage-0 text clears tg .. tc and fills fs; PC, Rc, Pc live to the end
+    static constexpr int tg = 0;
+    static constexpr int tt = tg + M;
+    static constexpr int tc = tt + M;
+    static constexpr int PC = tc + M;
+    static constexpr int Rc = PC + C;
+    static constexpr int Pc = Rc + kMaxActiveContacts * 9;
+    static constexpr int fs = Pc + kMaxActiveContacts * 3;
+    static constexpr int comp = fs + kMaxLevels * kMaxTaskDof;
+    static constexpr int q = ev(comp + 4);                     // N+1, stage 0 only
+    static constexpr int G = q + ev(N + 1);                    // N
+    static constexpr int hend = G + ev(N);
+    // ---- long-lived blocks
+    static constexpr int JbT = hend;                           // C x N
+    static constexpr int c_JC = JbT;                           // N x C, until Jbar^T is written over it
+    static constexpr int k_S = JbT;                            // N x 6
+    static constexpr int k_F = k_S + N * 6;                    // N x 6
+    static_assert(k_F + N * 6 <= JbT + C * N, "S and F borrow the Jbar^T region");
+    static constexpr int NwJw = JbT + C * N;                   // M x K
+    static constexpr int FNl = NwJw + M * K;                   // (C x K of the cycle: not formed here)
+    static constexpr int U = FNl + C * K;
+    static constexpr int Rw = U;                               // NB x 9, until the contact frames are taken
+    static constexpr int RE = U + max2(2 * M * T, NB * 9);
+    static_assert(Rw + NB * 9 <= RE, "the link rotations");
+    static constexpr int pw = RE;
+    static constexpr int aw = pw + NB * 3;
+    static constexpr int Rw0 = aw + NB * 3;                    // 9 (+1)
+    static constexpr int RF = ev(Rw0 + 10 + kMaxLevels * kMaxTaskLinks * 3);  // (behind the task points of the cycle)
+    static constexpr int c_Vb = RF;                            // M x K
+    static constexpr int RG = c_Vb + M * K + K * K;            // (behind G^-1 of the cycle)
+    // ---- stage 0
+    static constexpr int k_Iw = RF;                            // NB x 10 (first the ping-pong partner of pw)
+    static constexpr int k_Ic = k_Iw + NB * 10;                // NB x 10
+    static constexpr int k_Rl = k_Iw + NB * 3;                 // NB x 9: local rotations / ping-pong partner of Rw, dead before Iw and Ic are written
+    static constexpr int k_anc = k_Ic + NB * 10 - 2 * NB;      // ancestor indices at the tail of k_Ic
+    static_assert(k_Rl + NB * 9 <= k_anc, "local rotations must not reach the ancestor indices");
+    static constexpr bool a_overlay = false, a_packed = true;
+    static constexpr int k_A = RF;                             // N (N + 1) / 2, written after Ic has been consumed
+    static constexpr int Jcm = 0;                              // (COM task levels: full build of the cycle only)
+    // ---- the wrench maps and the QP (RE onwards; pw, aw, Vb and Y are dead by then)
+    static constexpr int WLD = 32;
+    static constexpr int FLD = 8;                              // row stride of FN: 1 + K columns, padded to an even number
+    static constexpr int t_in = RE;                            // M: tau_in (the `base` of the QP's torque rows)
+    static constexpr int wm = ev(t_in + M);                    // C x WLD
+    static constexpr int t_fv = wm + C * WLD;                  // C
+    static constexpr int qp_V = t_fv + C + C + K;              // kQpLd (the row a drop step passes through LDS; behind the cascade's t_wacc, t_cl)
+    static constexpr int qp_x = qp_V + kQpLd;
+    static constexpr int qp_end = qp_x + kQpLd;
+    // ---- stage 1
+    static constexpr int c_Y = RG;                             // N x C, dead once Jbar^T is written
+    static constexpr int RX = max2(c_Y + C * ev(N), ev(qp_end));
+    static_assert(c_Y + C * N <= RX, "Y ends before the small-inverse block");
+    static constexpr int c_s1 = RX;                            // max(C x K, 64): small-inverse scratch, sweep column (one double per lane)
+    static_assert(c_s1 % 2 == 0, "the sweep column is read in 16-byte pieces");
+    static constexpr int c_s2 = c_s1 + max2(C * K, 64);        // C x C: input of the small inverses, the four 6 x 6 blocks of NwJw
+    static constexpr int c_Lam = c_s2;
+    static constexpr int fn = c_s2;                            // C x FLD: Jbar[:, 6:] [tau_in | NwJw], world frame, kept for the wrench outputs
+    static constexpr int RXend = c_s2 + C * C;
+    static_assert(4 * K * K <= C * C, "JV, G^-1, B and S of the NwJw closed form");
+    static_assert(C * FLD <= C * C, "FN borrows the input block of the small inverses");
+    static_assert(qp_end <= fn, "QP scratch must not reach FN");
+    static_assert(1 + K <= FLD && 1 + K <= WLD, "columns of the wrench maps");
+    static constexpr int total = max2(RXend, max2(k_A + N * (N + 1) / 2, k_Ic + NB * 10));
+    static_assert(k_Ic + NB * 10 <= total && k_A + N * (N + 1) / 2 <= total, "stage-0 scratch");
+    static constexpr int total_bytes = total * (int)sizeof(real_t) + 64;
 };
+// at TOCABI's size this IS the compact map: nothing of the built-in constant-tree kernel moves
+#define DWBC_RD_SAME(X) (LdsRd<39, 34>::X == Lds3<39, 34, 1>::X)
+static_assert(DWBC_RD_SAME(tg) && DWBC_RD_SAME(PC) && DWBC_RD_SAME(Rc) && DWBC_RD_SAME(Pc) && DWBC_RD_SAME(fs) && DWBC_RD_SAME(comp) && DWBC_RD_SAME(q) &&
+                  DWBC_RD_SAME(G) && DWBC_RD_SAME(JbT) && DWBC_RD_SAME(c_JC) && DWBC_RD_SAME(k_S) && DWBC_RD_SAME(k_F) && DWBC_RD_SAME(NwJw) && DWBC_RD_SAME(Rw) &&
+                  DWBC_RD_SAME(pw) && DWBC_RD_SAME(aw) && DWBC_RD_SAME(Rw0) && DWBC_RD_SAME(c_Vb) && DWBC_RD_SAME(k_Iw) && DWBC_RD_SAME(k_Ic) && DWBC_RD_SAME(k_Rl) &&
+                  DWBC_RD_SAME(k_anc) && DWBC_RD_SAME(k_A) && DWBC_RD_SAME(wm) && DWBC_RD_SAME(t_fv) && DWBC_RD_SAME(qp_V) && DWBC_RD_SAME(qp_x) && DWBC_RD_SAME(c_Y) &&
+                  DWBC_RD_SAME(c_s1) && DWBC_RD_SAME(c_s2) && DWBC_RD_SAME(c_Lam) && DWBC_RD_SAME(total) && LdsRd<39, 34>::t_in == Lds3<39, 34, 1>::t_base,
+              "LdsRd<39, 34> is Lds3<39, 34, 1>");
+#undef DWBC_RD_SAME
 
 template <int N, int NB, int NT, class Topo>
 DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, const RedistIO &rio, int inst, real_t *L) {

@@ -96,14 +96,89 @@ def child(lib_path, what, B, steps):
     print(json.dumps(res), flush=True)
 
 
+PACK_MODELS = ("fixed_head", "fixed_arms", "surgery_43")  # tests/redist_pack_cases.py: 37 / 32, 23 / 18 and 43 / 38
+
+
+def pack_model(name, steps, out):
+    """A model that runs through a kernel pack: before the packs carried a redistribution kernel such a model's redistribution was refused,
+    so there is no earlier time; the yardstick is the same model's lean full cycle (solve(), dump off) in the same process at the same B --
+    the only launch a caller had, and the redistribution is a strict subset of its work.  Cycle and redistribution alternate, five windows
+    of `steps` launches each after a warm launch of both; medians.  Torque input: the cycle's own total torque pushed along the contact
+    null space by NwJw d, d = 10 N(0, I6) (every QP at work)."""
+    import tempfile
+
+    import numpy as np
+
+    import libdwbc_amd as D
+    from tests import cases
+    from tests.test_model_packs import VARIANTS, model_43, states_43, variant_states
+
+    from oracle import urdf_model
+
+    with tempfile.TemporaryDirectory() as tmp:
+        if name == "surgery_43":
+            md, _ = model_43()
+            links = [6, 12, 15]
+            states = lambda B: states_43(B, 7)
+        else:
+            path = cases.variant_urdf(os.path.join(tmp, name + ".urdf"), VARIANTS[name][0])
+            md, mo = D.Model.from_urdf(path), urdf_model.load_urdf(path)
+            links = [md.link_id(n) for n in ("L_AnkleRoll_Link", "R_AnkleRoll_Link", "Upperbody_Link")]
+            states = lambda B: variant_states(mo, B, seed=7)
+    cases.ensure_pack(md)
+    lines = [f"Redistribution of a caller-supplied torque against the lean full cycle of the same model ({name}: {md.ndof} dof / {md.nb} bodies;",
+             f"tools/redistribute_rate.py --model {name}): one MI355X, one process, cycle and redistribution alternating, five windows of {steps} launches each",
+             "after a warm launch of both; ms per launch.", ""]
+    for B in (1024, 8192):
+        wbc = D.Batch(md, B, device=0)
+        for cc, l in zip(cases.CONTACTS_2, links[:2]):
+            wbc.add_contact(l, cc["point"], cc["lx"], cc["ly"], cc["mu"], cc["muz"])
+        wbc.add_task(0, D.TASK_LINK_6D, 0)
+        wbc.add_task(1, D.TASK_LINK_ROTATION, links[2])
+        wbc.set_torque_limit(np.full(md.ndof - 6, 300.0))
+        q, fs = states(B)
+        wbc.set_state(q); wbc.set_contact(np.ones((B, 2), np.uint8)); wbc.set_fstar_all(fs)
+        wbc.enable_dump(True)
+        wbc.solve()
+        tau = wbc.get("tau").sum(axis=1) + np.einsum("bij,bj->bi", wbc.get("NwJw")[:, : md.ndof - 6, :6], 10.0 * np.random.default_rng(11).standard_normal((B, 6)))
+        wbc.enable_dump(False)
+        wbc.set_torque_input(tau)
+        wbc.solve(); wbc.redistribute(); wbc.sync()  # warm launches of the two kernels that are timed
+        runs = {"cycle": [], "redistribute": []}
+        for _ in range(5):
+            runs["cycle"].append(wbc.time_solves(steps) / steps)
+            runs["redistribute"].append(wbc.time_redistributes(steps) / steps)
+        st_c, st_r, cf = wbc.get("status"), wbc.get("redist_status"), wbc.get("redist_cf")
+        med = {k: statistics.median(v) for k, v in runs.items()}
+        for what, kernel, okf in (("cycle", wbc.kernel_name(), float(st_c.mean())), ("redistribute", wbc.redistribute_kernel_name(), float(st_r.mean()))):
+            extra = f", QP at work on {float((np.linalg.norm(cf, axis=1) > 1e-3).mean()):.3f}" if what == "redistribute" else ""
+            lines.append(f"B = {B:5d}  {what:13s} {' '.join(f'{x:7.4f}' for x in runs[what])}   median {med[what]:7.4f} ms -> {B / med[what] / 1e3:7.3f} M instances/s"
+                         f"   status ok {okf:.3f}{extra}   {kernel}")
+        r = med["redistribute"] / med["cycle"]
+        lines.append(f"B = {B}: redistribution {med['redistribute']:.4f} ms against the lean cycle's {med['cycle']:.4f} ms ({r:.3f} of it): {'not slower' if r <= 1.0 else 'SLOWER'}")
+        lines.append("")
+        wbc.close()
+    text = "\n".join(lines)
+    print(text, end="")
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent-lib", required=True, help="libdwbc_hip.so built from the parent commit")
+    ap.add_argument("--model", choices=PACK_MODELS, help="a kernel-pack model instead of TOCABI: against its own lean full cycle (no parent library needed)")
+    ap.add_argument("--parent-lib", help="libdwbc_hip.so built from the parent commit (TOCABI)")
     ap.add_argument("--lib", default=os.path.join(ROOT, "libdwbc_amd", "libdwbc_hip.so"))
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--out")
     ap.add_argument("--child", nargs=3, metavar=("LIB", "WHAT", "B"))
     args = ap.parse_args()
+    if args.model:
+        pack_model(args.model, args.steps, args.out)
+        return
+    if not args.parent_lib:
+        ap.error("--parent-lib is required without --model")
     if args.child:
         child(args.child[0], args.child[1], int(args.child[2]), args.steps)
         return

@@ -1,4 +1,5 @@
-"""Randomised parity sweep of the kernel packs (models of other sizes) against the numpy restatement: every instance compared.
+"""Randomised parity sweep of the kernel packs (models of other sizes) against the numpy restatement, the full cycle and the
+redistribution of a supplied torque: every instance compared.
 Development / profiles only."""
 import os
 import sys
@@ -9,6 +10,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import libdwbc_amd as D  # noqa: E402
 from oracle import urdf_model  # noqa: E402
 from tests import cases  # noqa: E402
+from tests import redist_cases as rc  # noqa: E402
+from tests import redist_pack_cases as pc  # noqa: E402
 from tests.test_model_packs import VARIANTS, model_43, oracle_cycle, states_43, variant_states, variant_urdf  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
@@ -46,3 +49,28 @@ for name in ("fixed_arms", "fixed_head", "plus4"):
             ok += 1
             worst = max(worst, float(np.abs(tau[b] - np.stack([o["tau_grav"], o["tau_task"], o["tau_contact"]])).max()))
     print(f"{name:10s} ({md.ndof} dof)  instances {B}  status mismatches {mism}  ok {ok}  max|tau - oracle| {worst:.3e}")
+    # redistribution of a supplied torque (the pack's dwbc_redistribute_kernel) on the same states: the restatement's own cycle torque
+    # pushed along the contact null space by NwJw d, d = 10 N(0, I6); every fifth instance on one foot
+    flags = np.ones((B, 2), np.uint8)
+    flags[2::10, 1] = 0
+    flags[7::10, 0] = 0
+    d = 10.0 * np.random.default_rng(11).standard_normal((B, 6))
+    cyc = pc.cycle_of(mo, links)
+    tau_in = np.zeros((B, md.ndof - 6))
+    refs = []
+    for b in range(B):
+        tau_in[b] = cyc.run(q[b], [bool(f) for f in flags[b]], [fs[b, :6], fs[b, 6:9]])
+        if flags[b].all():
+            tau_in[b] += cyc.NwJw @ d[b]
+        refs.append(rc.redistribute_ref(cyc, q[b], flags[b], tau_in[b]))
+    wbc.set_contact(flags)
+    wbc.set_torque_input(tau_in)
+    wbc.redistribute()
+    rt, rw, rs = wbc.get("redist_tau"), wbc.get("redist_wrench"), wbc.get("redist_status")
+    mism = sum(int(rs[b] != refs[b][0]) for b in range(B))
+    okb = [b for b in range(B) if rs[b] == refs[b][0] == 1]
+    busy = sum(np.linalg.norm(refs[b][2]) > 1e-3 for b in okb)
+    e_tau = max(float(np.abs(rt[b] - refs[b][1]).max()) for b in okb)
+    e_wr = max(float(np.abs(rw[b] - refs[b][3]).max()) for b in okb)
+    print(f"{'':10s} redistribution  {wbc.redistribute_kernel_name()}  status mismatches {mism}  ok {len(okb)}  QP at work on {busy}  "
+          f"max|tau - restatement| {e_tau:.3e}  max|wrench - restatement| {e_wr:.3e}")
