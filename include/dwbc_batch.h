@@ -283,6 +283,43 @@ int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float
 /* name of the kernel dwbc_batch_redistribute launches on this batch ("" and dwbc_last_error when it would be refused) */
 const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b);
 
+/* ---- CalcGravCompensation() as a call of its own, and ahead of the redistribution (reference include/dwbc.h:246-247,
+ * src/dwbc.cpp:875-889, src/wbd.cpp:186-192): the third call of a caller whose torque does not come from the task cascade --
+ * UpdateKinematics, SetContact, CalcContactConstraint, CalcGravCompensation, CalcContactRedistribute(torque_grav_ + u), getContactForce --
+ * with no task space and one A^-1 sweep per control step.  One lean kernel (the redistribution kernel's stages with torque_grav_ formed
+ * from P_C, J_C and the internal-wrench basis; no W, no W^+, no task level) in two forms:
+ *   dwbc_batch_grav_compensation(b)                       torque_grav_ and getContactForce(torque_grav_); no torque input, no QP
+ *   dwbc_batch_redistribute(b, flags | DWBC_REDIST_ADD_GRAVITY)   the torque input is a command ON TOP OF gravity compensation: the
+ *       redistribution of dwbc_batch_redistribute runs on torque_grav_ + torque_input (DWBC_REDIST_WRENCH row 0 is
+ *       getContactForce(torque_grav_ + torque_input), row 1 the same after NwJw c), and the three outputs below are written as well.
+ *       dwbc_batch_time_redistribute takes the bit too; dwbc_batch_redistribute_kernel_name reports the plain kernel,
+ *       dwbc_batch_grav_kernel_name the one either form launches.  Without the bit the three redistribution entry points are what they were.
+ * Outputs (buffer slots of their own, no dwbc_field; batch-major):
+ *   DWBC_GRAV_TAU (m) f64       torque_grav_
+ *   DWBC_GRAV_WRENCH (12) f64   getContactForce(torque_grav_) = Jbar^T[:, 6:] torque_grav_ - P_C, zero padded
+ *   DWBC_GRAV_STATUS (1) i32
+ * Per instance: one or two active contacts -> torque_grav_, its wrench, status 1; no contact -> zeros, status 1 (torque_grav_ is exactly
+ * zero there); more flags raised than two, or a failed contact stage -> zeros, status 0.
+ * The launch reads the state, the contact flags and (with the bit) the torque input, the torque limits and the per-instance parameters;
+ * it allocates its outputs before its first run and names no output of dwbc_batch_solve, of the plain dwbc_batch_redistribute's inputs
+ * beyond those, or of the link query, so all four may be called on one batch in any order.  dwbc_batch_copy_kinematics does not copy it.
+ * Refused (dwbc_last_error), in this order: DWBC_F32 batches, dwbc_batch_set_max_active_contacts(b, 3), a model without the kernel (built
+ * in for TOCABI's size on its own tree and on any; every kernel pack carries its size's).  With the bit the refusals of
+ * dwbc_batch_redistribute come first, with their messages.  dwbc_batch_get_grav before the first launch is refused.
+ * Not built: fp32, a third contact, hqp = false (DWBC_SOLVE_HQP clear), the reduced path's ReducedCalcGravCompensation.  The facade's
+ * DWBC::RobotData::CalcGravCompensation keeps being served from its cycle. */
+enum { DWBC_REDIST_ADD_GRAVITY = 8 };  /* a bit of the `flags` of the three redistribution entry points, beside DWBC_SOLVE_* */
+enum dwbc_grav_output { DWBC_GRAV_TAU = 0, DWBC_GRAV_WRENCH = 1, DWBC_GRAV_STATUS = 2 };
+int dwbc_batch_grav_compensation(dwbc_batch *b);                  /* asynchronous on the batch's stream */
+size_t dwbc_batch_grav_bytes(const dwbc_batch *b, int what);      /* of all B instances; 0: no such output */
+int dwbc_batch_get_grav(dwbc_batch *b, int what, void *host_out, size_t bytes);  /* synchronises the stream */
+/* zero-copy: a caller-owned DEVICE buffer of dwbc_batch_grav_bytes(b, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_grav(dwbc_batch *b, int what, void *device_ptr);
+/* name of the kernel dwbc_batch_grav_compensation launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_grav_kernel_name(const dwbc_batch *b);
+/* K back-to-back gravity-only launches bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_grav(dwbc_batch *b, int steps, float *ms);
+
 /* ---- UpdateKinematics as a call of its own (reference include/dwbc.h, src/dwbc.cpp:279-371): what a caller reads between it and
  * SetTaskSpace -- link_[i].xpos / rotm / v / w / jac_ and com_pos -- for a set of queried links, in one lean kernel (forward kinematics;
  * no mass-matrix inverse, no contact stage, no QP).  A query is up to 16 entries (link, point in the link's frame); link =

@@ -102,6 +102,13 @@ SYMBOLS = [
     ("dwbc_batch_redistribute", _i, [_vp, C.c_uint]),
     ("dwbc_batch_time_redistribute", _i, [_vp, C.c_uint, _i, C.POINTER(C.c_float)]),
     ("dwbc_batch_redistribute_kernel_name", C.c_char_p, [_vp]),
+    # gravity compensation in a launch of its own (and ahead of the redistribution: a bit of dwbc_batch_redistribute's flags)
+    ("dwbc_batch_grav_compensation", _i, [_vp]),
+    ("dwbc_batch_grav_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_batch_get_grav", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_bind_grav", _i, [_vp, _i, _vp]),
+    ("dwbc_batch_grav_kernel_name", C.c_char_p, [_vp]),
+    ("dwbc_batch_time_grav", _i, [_vp, _i, C.POINTER(C.c_float)]),
     # link poses, velocities and Jacobians in a launch of their own
     ("dwbc_batch_set_link_query", _i, [_vp, _i, _vp, _vp, _i]),
     ("dwbc_batch_update_kinematics", _i, [_vp]),

@@ -10,6 +10,7 @@
     tau = wbc.get("tau_total")
     wbc.set_torque_input(tau_policy); wbc.redistribute()   # CalcContactRedistribute(torque_input): any torque, its own lean kernel
     tau_policy + wbc.get("redist_tau")
+    wbc.grav_compensation(); wbc.grav_outputs()["tau"]       # CalcGravCompensation on its own; redistribute(add_gravity=True) adds it to the input
     wbc.set_link_query([0, 23], jacobians=True); wbc.update_kinematics()   # UpdateKinematics on its own: link_[i].xpos / rotm / v / w / jac_
     wbc.link_states()["rot"]
 
@@ -27,6 +28,8 @@ TASK_LINK_6D, TASK_LINK_6D_COM_FRAME, TASK_LINK_6D_CUSTOM_FRAME = 0, 1, 2
 TASK_LINK_POSITION, TASK_LINK_POSITION_COM_FRAME, TASK_LINK_POSITION_CUSTOM_FRAME = 3, 4, 5
 TASK_LINK_ROTATION, TASK_LINK_ROTATION_CUSTOM_FRAME = 6, 7
 SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
+REDIST_ADD_GRAVITY = 8  # a bit of the redistribution entry points' flags
+GRAV_OUTPUTS = {"tau": 0, "wrench": 1, "status": 2}  # enum dwbc_grav_output
 LINK_QUERY_OUTPUTS = {"pos": 0, "rot": 1, "vel": 2, "jac": 3}  # enum dwbc_link_query_output
 
 
@@ -390,17 +393,19 @@ class Batch:
         assert t.shape == (self.B, self.m), t.shape
         _check(self._L.dwbc_batch_set_torque_input(self._h, t.ctypes.data))
 
-    def redistribute(self, hqp=True, init=True):
+    def redistribute(self, hqp=True, init=True, add_gravity=False):
         """The contact-null-space torque NwJw c that brings the contact wrenches of the supplied torque back inside the ZMP / friction
         rows and the torque limits (reference include/dwbc.h:297, src/dwbc.cpp:1377-1568): get("redist_tau") (B, m), the QP's answer
         get("redist_cf") (B, 6), the wrench before and after the correction get("redist_wrench") (B, 2, 12), get("redist_status").
         One lean kernel on the batch's stream, asynchronous; reads the state, contact flags and torque limit of the batch and leaves
-        every output of solve() alone.  init=False is accepted and runs cold; hqp=False is refused."""
-        _check(self._L.dwbc_batch_redistribute(self._h, (SOLVE_HQP if hqp else 0) | (SOLVE_INIT if init else 0)))
+        every output of solve() alone.  init=False is accepted and runs cold; hqp=False is refused.
+        add_gravity: the torque input is a command on top of gravity compensation -- torque_grav_ + torque_input is redistributed in
+        the same launch (row 0 of "redist_wrench" is its wrench), and grav_outputs() are written as well."""
+        _check(self._L.dwbc_batch_redistribute(self._h, (SOLVE_HQP if hqp else 0) | (SOLVE_INIT if init else 0) | (REDIST_ADD_GRAVITY if add_gravity else 0)))
 
-    def time_redistributes(self, steps):
+    def time_redistributes(self, steps, add_gravity=False):
         ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_redistribute(self._h, SOLVE_HQP | SOLVE_INIT, int(steps), C.byref(ms)))
+        _check(self._L.dwbc_batch_time_redistribute(self._h, SOLVE_HQP | SOLVE_INIT | (REDIST_ADD_GRAVITY if add_gravity else 0), int(steps), C.byref(ms)))
         return ms.value
 
     def redistribute_kernel_name(self):
@@ -408,6 +413,52 @@ class Batch:
         if not name:
             raise DwbcError(_lib.last_error())
         return name
+
+    # ---- CalcGravCompensation on its own (reference include/dwbc.h:246-247, src/wbd.cpp:186-192)
+    def grav_compensation(self):
+        """torque_grav_ and getContactForce(torque_grav_) of the state and contact flags, in one lean kernel on the batch's stream,
+        asynchronous: no task space, no torque input, no QP.  Leaves every output of solve(), redistribute() and update_kinematics() as it
+        is.  No contact: zeros, status 1; more than two flags or a failed contact stage: zeros, status 0.  fp64, two contacts at most."""
+        _check(self._L.dwbc_batch_grav_compensation(self._h))
+
+    def _grav_shape(self, name):
+        return {"tau": ((self.B, self.m), np.float64), "wrench": ((self.B, 12), np.float64), "status": ((self.B,), np.int32)}[name]
+
+    def grav_outputs(self):
+        """dict of ``tau`` (B, m), ``wrench`` (B, 12) zero padded and ``status`` (B,) int32 of the last grav_compensation() or
+        redistribute(add_gravity=True); synchronises the stream"""
+        out = {}
+        for name, what in GRAV_OUTPUTS.items():
+            shape, dt = self._grav_shape(name)
+            a = np.zeros(shape, dt)
+            _check(self._L.dwbc_batch_get_grav(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def bind_grav(self, name, tensor):
+        """output ``name`` ("tau", "wrench": float64; "status": int32) into a caller-owned device tensor, written in place by every later
+        launch; None: back to a buffer of the batch's own"""
+        what = GRAV_OUTPUTS[name]
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_grav(self._h, what, None))
+            self._keep.pop("grav_" + name, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = self._L.dwbc_batch_grav_bytes(self._h, what)
+        assert tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(self._L.dwbc_batch_bind_grav(self._h, what, C.c_void_p(tensor.data_ptr())))
+        self._keep["grav_" + name] = tensor
+
+    def grav_kernel_name(self):
+        name = self._L.dwbc_batch_grav_kernel_name(self._h).decode()
+        if not name:
+            raise DwbcError(_lib.last_error())
+        return name
+
+    def time_grav(self, steps):
+        ms = C.c_float(0)
+        _check(self._L.dwbc_batch_time_grav(self._h, int(steps), C.byref(ms)))
+        return ms.value
 
     # ---- UpdateKinematics on its own: poses, velocities and Jacobians of queried links before any f* is set
     def set_link_query(self, links, points=None, jacobians=False):

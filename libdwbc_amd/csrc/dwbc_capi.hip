@@ -779,39 +779,85 @@ static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
     return 1;
 }
 
-// uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
-static int redistribute_once(dwbc_batch *b, unsigned flags, dwbc_plan::Plan *planned) {
-    // (DWBC_SOLVE_INIT clear is accepted: the one QP is strictly convex and starts cold either way)
-    const dwbc_plan::Plan p = redist_plan(b, (flags & DWBC_SOLVE_HQP) != 0);
-    if (!p.row) return fail(p.err);
-    if (flags & DWBC_SOLVE_REDUCED) return fail("redistribution of a supplied torque: not built on the reduced dynamics path");
-    if (b->su.n_contacts < 1) return fail("no contact constraint");
-    if (!b->tau_in_set) return fail("no torque input: call dwbc_batch_set_torque_input (or bind DWBC_IN_TORQUE) first");
-    HIP_OK(hipSetDevice(b->device));
-    if (!upload_inputs(b)) return 0;
-    bool queued = false;
-    if (!send(b, fld::kTauIn, &queued)) return 0;
-    if (queued && !mark_upload(b)) return 0;
-    for (const int f : {DWBC_REDIST_TAU, DWBC_REDIST_CF, DWBC_REDIST_WRENCH, DWBC_REDIST_STATUS})
-        if (!ensure_field(b, f)) return 0;
-    if (planned) *planned = p;
-    return launch_redistribute(b, p);
+static int read_back(dwbc_batch *b, const void *src, void *out, size_t nbytes);
+// ---- CalcGravCompensation on its own, or ahead of the redistribution of a command on top of it: dwbc_redistribute.h with GRAV = true
+static dwbc_plan::Plan grav_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.grav_comp = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
 }
 
-int dwbc_batch_redistribute(dwbc_batch *b, unsigned flags) { return redistribute_once(b, flags, nullptr); }
+size_t dwbc_batch_grav_bytes(const dwbc_batch *b, int what) {
+    const size_t per[3] = {(size_t)b->m * sizeof(double), 12 * sizeof(double), sizeof(int)};
+    return what >= DWBC_GRAV_TAU && what <= DWBC_GRAV_STATUS ? (size_t)b->B * per[what] : 0;
+}
 
-int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float *ms) {
+// the outputs exist before the first launch writes them (bound ones stay bound)
+static int ensure_grav_outputs(dwbc_batch *b) {
+    for (int w = DWBC_GRAV_TAU; w <= DWBC_GRAV_STATUS; w++)
+        if (!b->buf[fld::kGvTau + w].d && !ensure(b->buf[fld::kGvTau + w], dwbc_batch_grav_bytes(b, w))) return 0;
+    return 1;
+}
+
+// with_input: the redistribution of torque_grav_ + torque input goes with it
+static int launch_grav(dwbc_batch *b, const dwbc_plan::Plan &p, bool with_input) {
+    const void *fn = p.row->fn;
+    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        b->lds_attr_set.push_back(fn);
+    }
+    BatchIO io{};  // what stage 0 and the contact stage read; no buffer of the cycle or of the link query is named
+    io.B = b->B;
+    io.q = b->dev<double>(fld::kQ);
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.fstar = b->dev<double>(fld::kFstar);
+    io.body = b->d_body;
+    io.topo = b->d_topo;
+    io.hqp = 1;
+    io.pair_swap_bit = -1;
+    io.inst_par = with_input ? b->dev<double>(fld::kInstPar) : nullptr;  // (QP rows alone read the record)
+    Setup su_rec;
+    GravIO gio{};
+    if (with_input) {
+        gio.tau_in = b->dev<double>(fld::kTauIn);
+        gio.rd_tau = b->dev<double>(fld::kRdTau);
+        gio.rd_cf = b->dev<double>(fld::kRdCf);
+        gio.rd_wrench = b->dev<double>(fld::kRdWrench);
+        gio.rd_status = b->dev<int>(fld::kRdStatus);
+    }
+    gio.tau = b->dev<double>(fld::kGvTau);
+    gio.wrench = b->dev<double>(fld::kGvWrench);
+    gio.status = b->dev<int>(fld::kGvStatus);
+    void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io, (void *)&gio};
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    b->gv_ran = true;
+    return 1;
+}
+
+// uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+static int grav_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
+    const dwbc_plan::Plan p = grav_plan(b);
+    if (!p.row) return fail(p.err);
+    if (b->su.n_contacts < 1) return fail("no contact constraint");
     HIP_OK(hipSetDevice(b->device));
-    dwbc_plan::Plan p{};
-    if (!redistribute_once(b, flags, &p)) return 0;  // uploads + warm launch
+    if (!upload_inputs(b)) return 0;  // (the state and the flags are read; stage 0 stages f* of a batch that has task levels)
+    if (!ensure_grav_outputs(b)) return 0;
+    if (planned) *planned = p;
+    return launch_grav(b, p, false);
+}
+
+int dwbc_batch_grav_compensation(dwbc_batch *b) { return grav_once(b, nullptr); }
+
+// K launches bracketed by HIP events on the batch's stream; the events are destroyed on every way out (a failed step has set the error string)
+// mode 0: the plain redistribution, 1: gravity compensation alone, 2: gravity compensation and the redistribution on top of it
+static int time_launches(dwbc_batch *b, int steps, float *ms, const dwbc_plan::Plan &p, int mode) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    // the events are destroyed on every way out (a failed step has set the error string)
     auto timed = [&]() -> int {
         HIP_OK(hipEventCreate(&e0));
         HIP_OK(hipEventCreate(&e1));
         HIP_OK(hipEventRecord(e0, b->stream));
         for (int i = 0; i < steps; i++)
-            if (!launch_redistribute(b, p)) return 0;
+            if (!(mode == 0 ? launch_redistribute(b, p) : launch_grav(b, p, mode == 2))) return 0;
         HIP_OK(hipEventRecord(e1, b->stream));
         HIP_OK(hipEventSynchronize(e1));
         HIP_OK(hipEventElapsedTime(ms, e0, e1));
@@ -821,6 +867,75 @@ int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     return ok;
+}
+
+int dwbc_batch_time_grav(dwbc_batch *b, int steps, float *ms) {
+    HIP_OK(hipSetDevice(b->device));
+    dwbc_plan::Plan p{};
+    if (!grav_once(b, &p)) return 0;  // uploads + warm launch
+    return time_launches(b, steps, ms, p, 1);
+}
+
+const char *dwbc_batch_grav_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = grav_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
+
+int dwbc_batch_get_grav(dwbc_batch *b, int what, void *out, size_t bytes) {
+    const size_t need = dwbc_batch_grav_bytes(b, what);
+    if (need == 0) return fail("gravity compensation: unknown output");
+    if (!b->gv_ran) return fail("no gravity-compensation output yet: call dwbc_batch_grav_compensation (or dwbc_batch_redistribute with DWBC_REDIST_ADD_GRAVITY) first");
+    if (bytes < need) return fail("output buffer too small");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kGvTau + what].d, out, need);
+}
+
+int dwbc_batch_bind_grav(dwbc_batch *b, int what, void *p) {
+    const size_t need = dwbc_batch_grav_bytes(b, what);
+    if (need == 0) return fail("gravity compensation: unknown output");
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kGvTau + what];
+    release(u);
+    b->gv_ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, need);
+    u.d = p;
+    return 1;
+}
+
+// uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+// DWBC_REDIST_ADD_GRAVITY: every refusal of the plain redistribution first, then the gravity-compensation kernel in its place
+static int redistribute_once(dwbc_batch *b, unsigned flags, dwbc_plan::Plan *planned) {
+    // (DWBC_SOLVE_INIT clear is accepted: the one QP is strictly convex and starts cold either way)
+    dwbc_plan::Plan p = redist_plan(b, (flags & DWBC_SOLVE_HQP) != 0);
+    if (!p.row) return fail(p.err);
+    if (flags & DWBC_SOLVE_REDUCED) return fail("redistribution of a supplied torque: not built on the reduced dynamics path");
+    if (b->su.n_contacts < 1) return fail("no contact constraint");
+    if (!b->tau_in_set) return fail("no torque input: call dwbc_batch_set_torque_input (or bind DWBC_IN_TORQUE) first");
+    const bool grav = (flags & DWBC_REDIST_ADD_GRAVITY) != 0;
+    if (grav && !(p = grav_plan(b)).row) return fail(p.err);
+    HIP_OK(hipSetDevice(b->device));
+    if (!upload_inputs(b)) return 0;
+    bool queued = false;
+    if (!send(b, fld::kTauIn, &queued)) return 0;
+    if (queued && !mark_upload(b)) return 0;
+    for (const int f : {DWBC_REDIST_TAU, DWBC_REDIST_CF, DWBC_REDIST_WRENCH, DWBC_REDIST_STATUS})
+        if (!ensure_field(b, f)) return 0;
+    if (grav && !ensure_grav_outputs(b)) return 0;
+    if (planned) *planned = p;
+    return grav ? launch_grav(b, p, true) : launch_redistribute(b, p);
+}
+
+int dwbc_batch_redistribute(dwbc_batch *b, unsigned flags) { return redistribute_once(b, flags, nullptr); }
+
+int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float *ms) {
+    HIP_OK(hipSetDevice(b->device));
+    dwbc_plan::Plan p{};
+    if (!redistribute_once(b, flags, &p)) return 0;  // uploads + warm launch
+    return time_launches(b, steps, ms, p, (flags & DWBC_REDIST_ADD_GRAVITY) ? 2 : 0);
 }
 
 const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b) {

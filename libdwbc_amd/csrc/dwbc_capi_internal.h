@@ -124,6 +124,7 @@ struct dwbc_batch {
     int lq_n = 0, lq_link[16] = {};
     double lq_point[16][3] = {};
     bool lq_jac = false, lq_ran = false;
+    bool gv_ran = false;  // a gravity-compensation launch (alone or ahead of a redistribution) has filled the DWBC_GRAV_* outputs
     dwbc::DumpLayout dl{};
 };
 

@@ -13,9 +13,10 @@ using namespace dwbc;
 
 // device buffers of a batch that are owned or bound, sized once and uploaded from a host mirror if they have one: the bindable fields,
 // the diagnostics record, and the inputs that are no field -- the task-reference inputs and the per-instance parameter record
-// and the four outputs of a link query, which are no field either (dwbc_batch::buf is indexed by this)
+// and the four outputs of a link query and the three of a gravity compensation, which are no field either (dwbc_batch::buf is indexed by this)
 enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kInstPar,
-            kLqPos, kLqRot, kLqVel, kLqJac, kSlotCount };
+            kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kSlotCount };
+static_assert(kGvWrench == kGvTau + DWBC_GRAV_WRENCH && kGvStatus == kGvTau + DWBC_GRAV_STATUS, "kGvTau + dwbc_grav_output");
 static_assert(kLqRot == kLqPos + DWBC_LQ_ROT && kLqVel == kLqPos + DWBC_LQ_VEL && kLqJac == kLqPos + DWBC_LQ_JAC, "kLqPos + dwbc_link_query_output");
 
 // one extent of a shape: mul * var + add

@@ -98,6 +98,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
     redistribute_instance<N, NB, 64, Topo>(th, su, io, rio, inst, lds);
 }
 
+// gravity compensation, alone or with the redistribution of a command on top of it (dwbc_redistribute.h, GRAV = true): the redistribution
+// kernel's stages with torque_grav_ formed behind P_C, on the same map (LdsGc adds tenants, no bytes) and under the same register cap.  One
+// instantiation serves both forms: without GravIO::tau_in NwJw and the QP are skipped by a wave-uniform branch
+template <int N, int NB, class Topo>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_gravcomp_kernel(const Setup su, const BatchIO io, const GravIO gio) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    const RedistIO rio{gio.tau_in, gio.rd_tau, gio.rd_cf, gio.rd_wrench, gio.rd_status};
+    redistribute_instance<N, NB, 64, Topo, true>(th, su, io, rio, inst, lds, &gio);
+}
+
 // link poses, velocities and Jacobians in a launch of their own (dwbc_link_query.h): forward kinematics and, for the COM link, the six
 // base rows of A -- 13 KB of LDS, no register cap; the tree is read at run time
 template <int N, int NB>
@@ -159,6 +172,13 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_REDIST(N, NB, TOPO, TK) \
     DWBC_ROW(N, NB, 0, TK, kRedist, 0u, (LdsRd<N, NB>::total_bytes), kNT, dwbc_redistribute_kernel, N, NB, dwbc::TOPO),
 #endif
+// the gravity-compensation kernel: wherever the redistribution kernel is
+#ifdef DWBC_NO_REDIST_KERNEL
+#define DWBC_ROW_GRAVCOMP(N, NB, TOPO, TK)
+#else
+#define DWBC_ROW_GRAVCOMP(N, NB, TOPO, TK) \
+    DWBC_ROW(N, NB, 0, TK, kGravComp, 0u, (LdsGc<N, NB>::total_bytes), kNT, dwbc_gravcomp_kernel, N, NB, dwbc::TOPO),
+#endif
 // the link-query kernel: fp64, any tree of its size (DWBC_NO_LINK_QUERY_KERNEL: fp32); not part of a kernel pack
 #ifdef DWBC_NO_LINK_QUERY_KERNEL
 #define DWBC_ROW_LINK_QUERY(N, NB)
@@ -185,6 +205,7 @@ const lp::Row kRows[] = {
 #endif
     DWBC_ROW_GC(39, 34, 6, 0u) DWBC_ROW_GC(39, 34, 12, lp::kWideTasks)
     DWBC_ROW_REDIST(39, 34, TopoTocabi, 1) DWBC_ROW_REDIST(39, 34, TopoGeneric, 0)
+    DWBC_ROW_GRAVCOMP(39, 34, TopoTocabi, 1) DWBC_ROW_GRAVCOMP(39, 34, TopoGeneric, 0)
     DWBC_ROW_LINK_QUERY(39, 34)
 };
 #endif

@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque or a link query):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query or a gravity compensation):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -9,8 +9,9 @@ namespace dwbc_plan {
 
 enum Arith { kDouble = 0, kFloat = 1 };
 // full-model cycle, reduced (centroidal) dynamics, general-contact cycle, redistribution of a caller-supplied torque (dwbc_redistribute.h),
-// link poses / velocities / Jacobians on their own (dwbc_link_query.h)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4 };
+// link poses / velocities / Jacobians on their own (dwbc_link_query.h), gravity compensation alone or before such a redistribution
+// (dwbc_redistribute.h, GRAV = true)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -62,6 +63,10 @@ struct Request {
     // not a cycle either: UpdateKinematics on its own for a set of queried links (dwbc_batch_update_kinematics); of the members above it reads
     // the model and arith
     bool link_query = false;
+    // not a cycle either: CalcGravCompensation on its own, or ahead of the redistribution of a command on top of it
+    // (dwbc_batch_grav_compensation, dwbc_batch_redistribute with DWBC_REDIST_ADD_GRAVITY); of the members above it reads the model, arith
+    // and max_active (the caller plans the redistribution request as well where there is one: its refusals come first)
+    bool grav_comp = false;
 };
 
 struct Plan {
@@ -120,6 +125,14 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.arith == kFloat) return refuse("link query: fp64 batches only");
         const Row *r = Candidates(q, kLinkQuery, tabs, n_tabs).pick(0u, 0u);
         if (!r) return refuse("no link-query kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
+        return run(r, false);
+    }
+    // gravity compensation: planned like the redistribution below, whatever the batch size, the levels or the cycle's options are
+    if (q.grav_comp) {
+        if (q.arith == kFloat) return refuse("gravity compensation: fp64 batches only");
+        if (q.max_active > 2) return refuse("gravity compensation: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
+        const Row *r = Candidates(q, kGravComp, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no gravity-compensation kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         return run(r, false);
     }
     // redistribution of a caller-supplied torque: one lean kernel, whatever the batch size or the task set-up (it runs no task level and

@@ -41,6 +41,8 @@ static const dwbc_plan::Row kPack[] = {
 #endif
 // redistribution of a caller-supplied torque (dwbc_redistribute.h) of this model size and tree
     DWBC_ROW_REDIST(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
+// gravity compensation, alone or before that redistribution (dwbc_redistribute.h, GRAV = true)
+    DWBC_ROW_GRAVCOMP(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
 };
 
 #ifdef DWBC_PACK_PARENTS

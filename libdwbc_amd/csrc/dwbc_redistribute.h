@@ -12,6 +12,10 @@
 //                                                   (dwbc.cpp:1458-1517; qp_solve_wave, cold start at c = 0, accepted at kQpFeasTol)
 // What the cycle needs beyond that is never formed here: no A^-1 N_c (the register columns stay A^-1), no W, no W^+, no gravity torque,
 // no task block.
+// The GRAV build of the same text (redistribute_instance<.., true>, dwbc_gravcomp_kernel) is RobotData::CalcGravCompensation() as a launch
+// of its own and ahead of the redistribution: torque_grav_ is formed behind P_C from blocks stage 1 already holds (see above GravIO), the
+// redistribution then runs on torque_grav_ + tau_in, or is skipped when there is no tau_in.  Every GRAV branch is `if constexpr` or folds
+// on a constant in the plain build, whose instantiations compile to what they were.
 #pragma once
 #include "dwbc_cycle2.h"
 
@@ -132,9 +136,46 @@ static_assert(DWBC_RD_SAME(tg) && DWBC_RD_SAME(PC) && DWBC_RD_SAME(Rc) && DWBC_R
               "LdsRd<39, 34> is Lds3<39, 34, 1>");
 #undef DWBC_RD_SAME
 
-template <int N, int NB, int NT, class Topo>
-DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, const RedistIO &rio, int inst, real_t *L) {
+// ---- gravity compensation (GRAV = true): RobotData::CalcGravCompensation, reference include/dwbc.h:246-247, src/dwbc.cpp:875-889,
+// src/wbd.cpp:186-192 -- torque_grav_ = W^+ (A^-1 N_c G)[6:] without W or W^+.  W^+ a is constrained inverse dynamics, and
+// for a = G it collapses onto the blocks stage 1 holds, because Lambda_c (J_C A^-1 G) IS P_C.  With J_Cb / J_Cj the base / joint columns of J_C:
+//     cv = G_b - J_Cb^T P_C        y = (J_Cb^T J_Cb)^-1 cv       E = P_C + J_Cb y     (the contact wrench that balances the base rows; min norm)
+//     tau_any = G_j - J_Cj^T E     torque_grav_ = tau_any - Vb (Vb^T Vb)^-1 Vb^T tau_any   (two contacts: off the internal-wrench torques)
+// The launch has two forms.  Gravity only (GravIO::tau_in == nullptr): torque_grav_ and getContactForce(torque_grav_); NwJw and the QP are
+// skipped by a wave-uniform branch.  With a torque input: the redistribution below runs on torque_grav_ + tau_in, and torque_grav_ is
+// written as well.  No contact: torque_grav_ = 0 exactly (G = 9.81 A[2, :], so G_j - A_jb A_bb^-1 G_b = 0).
+// Device pointers of such a launch; the kernel's own argument struct beside BatchIO (RedistIO keeps its layout)
+struct GravIO {
+    const io_t *tau_in;  // B x M   command on top of gravity compensation, or nullptr: gravity only
+    io_t *rd_tau, *rd_cf, *rd_wrench;  // the redistribution's outputs as RedistIO has them (never written without tau_in)
+    int *rd_status;
+    io_t *tau;           // B x M   torque_grav_
+    io_t *wrench;        // B x 12  getContactForce(torque_grav_), zero padded
+    int *status;         // B       1 ok / 0: more flags than the capacity, or a failed contact stage
+};
+
+// Tenants of the gravity stage on LdsRd: every one moves into a block that is dead between P_C and NwJw, so the map and its bytes are
+// LdsRd's at every size (region : what it held : the tenant)
+//   tg    : zeros of stage 0 (the cycle's gravity torque)  : torque_grav_, to the end
+//   tt    : zeros of stage 0                               : tau_any
+//   c_Y   : Y = J_C A^-1, dead once Jbar^T is written      : J_C^T formed again (Jbar^T stands where stage 1 formed it)
+//   c_s1  : small-inverse scratch                          : cv, y, E, Vb^T tau_any and its solve (36 doubles)
+//   c_s2  : Lambda_c, dead once Jbar^T is written          : J_Cb^T J_Cb, Vb^T Vb and their inverses (4 x 36)
+//   fn    : column 7 of FN (padding of the 1 + K columns)  : Jbar[:, 6:] torque_grav_
+template <int N, int NB>
+struct LdsGc : LdsRd<N, NB> {
+    using R = LdsRd<N, NB>;
+    static constexpr int g_tau = R::tg, g_any = R::tt, g_JC = R::c_Y, g_v = R::c_s1, g_Q = R::c_s2;
+    static constexpr int g_col = R::FLD - 1;  // column of FN
+    static_assert(g_JC + R::C * N <= R::RX, "J_C again where Y was");
+    static_assert(36 <= R::c_s2 - R::c_s1 && 4 * 36 <= R::C * R::C, "vectors and 6 x 6 blocks of the gravity stage");
+    static_assert(g_col > R::K, "the padding column of FN");
+};
+
+template <int N, int NB, int NT, class Topo, bool GRAV = false>
+DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, const RedistIO &rio, int inst, real_t *L, const GravIO *gio = nullptr) {
     using S = LdsRd<N, NB>;
+    const bool has_in = !GRAV || rio.tau_in != nullptr;  // (the plain build: a constant)
     constexpr bool kExtras = false;
     constexpr int M = S::M, C = S::C, WLD = S::WLD, FLD = S::FLD;
     DWBC_LANE_DECL;
@@ -263,8 +304,74 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
     mv_n<NT>(th, L + S::PC, JbT, N, L + S::G, cd, N);  // P_C = Jbar^T G (wbd.cpp:192)
     DWBC_SYNC();
 
+    if constexpr (GRAV) {
+        // ================= torque_grav_ (wbd.cpp:186-191) from P_C, J_C and Vb: see above GravIO =================
+        using Sg = LdsGc<N, NB>;
+        real_t *JC2 = L + Sg::g_JC, *gv = L + Sg::g_v, *gq = L + Sg::g_Q, *tgv = L + Sg::g_tau, *tany = L + Sg::g_any;
+        real_t *cv = gv, *yv = gv + 6, *Ev = gv + 12, *wv = gv + 24, *zv = gv + 30;
+        const real_t *Gv = L + S::G, *PCv = L + S::PC;
+        if (nc > 0 && st_contact) {
+            for (int idx = th.tid; idx < C * N; idx += NT) JC2[idx] = real_t(0.0);
+            DWBC_SYNC();
+            for (int a = 0; a < nc; a++)
+                point_jacobian<N, NB, NT>(th, L + S::Rw0, L + S::pw, L + S::aw, topo, nb, su.c_link[act_c[a]], L + S::Pc + a * 3, JC2, 1, 6 * a, 6, 0, C);
+            DWBC_SYNC();
+            for (int idx = th.tid; idx < 42; idx += NT) {  // J_Cb^T J_Cb (6 x 6) and cv
+                if (idx < 36) {
+                    const int r = idx / 6, c = idx - r * 6;
+                    real_t acc = real_t(0.0);
+                    for (int p = 0; p < cd; p++) acc += JC2[r * C + p] * JC2[c * C + p];
+                    gq[idx] = acc;
+                } else {
+                    const int r = idx - 36;
+                    real_t acc = Gv[r];
+                    for (int p = 0; p < cd; p++) acc -= JC2[r * C + p] * PCv[p];
+                    cv[r] = acc;
+                }
+            }
+            DWBC_SYNC();
+            if (!spd_inverse_small(gq, 6, 6, gq + 36, 6, gv + 36)) st_contact = 0;
+            mv_n<NT>(th, yv, gq + 36, 6, cv, 6, 6);
+            DWBC_SYNC();
+            for (int p = th.tid; p < cd; p += NT) {
+                real_t acc = PCv[p];
+#pragma unroll
+                for (int r = 0; r < 6; r++) acc += JC2[r * C + p] * yv[r];
+                Ev[p] = acc;
+            }
+            DWBC_SYNC();
+            real_t *tdst = k > 0 ? tany : tgv;
+            for (int j = th.tid; j < M; j += NT) {
+                real_t acc = Gv[6 + j];
+                for (int p = 0; p < cd; p++) acc -= JC2[(6 + j) * C + p] * Ev[p];
+                tdst[j] = acc;
+            }
+            DWBC_SYNC();
+            if (k > 0) {
+                mm_tn<NT>(th, gq + 72, 6, Vb, 6, Vb, 6, 6, M, 6);  // Vb^T Vb
+                for (int a = th.tid; a < 6; a += NT) {
+                    real_t acc = real_t(0.0);
+                    _Pragma("unroll 8")
+                    for (int j = 0; j < M; j++) acc += Vb[j * 6 + a] * tany[j];
+                    wv[a] = acc;
+                }
+                DWBC_SYNC();
+                if (!spd_inverse_small(gq + 72, 6, 6, gq + 108, 6, gv + 36)) st_contact = 0;
+                mv_n<NT>(th, zv, gq + 108, 6, wv, 6, 6);
+                DWBC_SYNC();
+                for (int j = th.tid; j < M; j += NT) {
+                    real_t acc = tany[j];
+#pragma unroll
+                    for (int a = 0; a < 6; a++) acc -= Vb[j * 6 + a] * zv[a];
+                    tgv[j] = acc;
+                }
+                DWBC_SYNC();
+            }
+        }
+    }
+
     // ================= NwJw from the closed-form internal-wrench basis (see dwbc_cycle2.h): NwJw = Vb G^-1 X^T, X = S^-1 JV =================
-    if (k > 0) {
+    if (k > 0 && has_in) {
         static_assert(kMaxActiveContacts == 2, "k in {0, 6}");
         constexpr int K6 = 6;
         for (int idx = th.tid; idx < K6 * K6; idx += NT) {
@@ -294,15 +401,19 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
     // ================= the wrench maps of [tau_in | NwJw] and the QP (dwbc.cpp:1458-1517) =================
     const io_t *tin_g = rio.tau_in + (size_t)inst * M;
     real_t *tin = L + S::t_in, *FN = L + S::fn, *WM = L + S::wm, *fv = L + S::t_fv;
+    if constexpr (GRAV) {  // the torque that is redistributed: torque_grav_ + the command (gravity only: torque_grav_)
+        for (int i = th.tid; i < M; i += NT) tin[i] = L[LdsGc<N, NB>::g_tau + i] + (has_in ? (real_t)tin_g[i] : real_t(0.0));
+    } else
     for (int i = th.tid; i < M; i += NT) tin[i] = (real_t)tin_g[i];
     DWBC_SYNC();
-    const int ncol = 1 + k;
+    const int ncol = has_in ? 1 + k : 1;
+    constexpr int gcol = GRAV ? LdsGc<N, NB>::g_col : -1;  // the wrench map of torque_grav_ alone, in the padding column of FN
     for (int idx = th.tid; idx < cd * FLD; idx += NT) {
         const int i = idx / FLD, col = idx - i * FLD;
         real_t acc = real_t(0.0);
-        if (col < ncol) {
-            const real_t *rhs = col == 0 ? tin : L + S::NwJw + (col - 1);
-            const int rs = col == 0 ? 1 : 6;
+        if (col < ncol || col == gcol) {
+            const real_t *rhs = col == 0 ? tin : col == gcol ? L + S::tg : L + S::NwJw + (col - 1);
+            const int rs = (col == 0 || col == gcol) ? 1 : 6;
             _Pragma("unroll 8")
             for (int c = 0; c < M; c++) acc += JbT[i * N + 6 + c] * rhs[c * rs];
         }
@@ -325,7 +436,7 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
     DWBC_SYNC();
     int st_redis = 1;
     real_t xq[6] = {real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0)};
-    if (k > 0 && st_contact) {
+    if (k > 0 && st_contact && has_in) {
         const int nlim = su.has_tau_lim ? 2 * M : 0, ncone = 10 * nc;
         QpResult qres;
         PL(real_t, sfin);
@@ -342,6 +453,14 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
 
     // ================= outputs =================
     const bool ok = st_contact && st_redis;
+    if constexpr (GRAV) {
+        io_t *gt = gio->tau + (size_t)inst * M;
+        for (int i = th.tid; i < M; i += NT) gt[i] = st_contact ? L[LdsGc<N, NB>::g_tau + i] : real_t(0.0);
+        io_t *gw = gio->wrench + (size_t)inst * 12;
+        for (int i = th.tid; i < 12; i += NT) gw[i] = (i < cd && st_contact) ? FN[i * FLD + gcol] - L[S::PC + i] : real_t(0.0);  // wbd.cpp:268-271
+        if (th.tid == 0) gio->status[inst] = st_contact ? 1 : 0;
+        if (!has_in) return;
+    }
     io_t *tau = rio.tau + (size_t)inst * M;
     for (int i = th.tid; i < M; i += NT) {
         real_t c = real_t(0.0);
