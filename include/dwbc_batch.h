@@ -348,6 +348,45 @@ int dwbc_batch_bind_link_query(dwbc_batch *b, int what, void *device_ptr);
 /* name of the kernel dwbc_batch_update_kinematics launches on this batch ("" and dwbc_last_error when it would be refused) */
 const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b);
 
+/* ---- the dynamics half of UpdateKinematics as a call of its own (reference src/dwbc.cpp:279-371): what a caller reads off RobotData
+ * after it -- rd_.A_, A_inv_, B_, G_, CMM_, com_pos (the reference's harnesses: torque = A_.bottomRows(m) jacc + J_C^T f + B_.tail(m),
+ * y = -A_inv_ B_, CMM_ q_dot) -- in one lean kernel (stage 0 of the cycle: kinematics, CRBA, the A^-1 sweep; the RNEA of B_; the centroidal
+ * block.  No contact stage, no task level, no QP).  The caller asks for a set of outputs; what is not asked for is not computed:
+ * without DWBC_DYN_A_INV there is no sweep, without DWBC_DYN_B (or without a qdot) no RNEA, without DWBC_DYN_CMM / DWBC_DYN_COM no
+ * centroidal block.  Outputs (buffer slots of their own, no dwbc_field; batch-major):
+ *   DWBC_DYN_A (n, n) f64       A_
+ *   DWBC_DYN_A_INV (n, n) f64   A_inv_
+ *   DWBC_DYN_B (n) f64          B_ = C qdot + g; while the state was set without a qdot, G_ to the bit (B_(q, 0) = G_)
+ *   DWBC_DYN_G (n) f64          G_
+ *   DWBC_DYN_CMM (6, n) f64     CMM_
+ *   DWBC_DYN_COM (3) f64        com_pos
+ *   DWBC_DYN_STATUS (1) i32     always written; 0 only if DWBC_DYN_A_INV was asked for and the sweep met a pivot that is not positive:
+ *                               every asked-for output of that instance is then zero
+ * The launch reads the state and the model alone: it needs no contact and no task space, dwbc_batch_set_max_active_contacts does not
+ * matter to it, and it names no buffer of dwbc_batch_solve, dwbc_batch_redistribute, dwbc_batch_grav_compensation or the link query --
+ * their outputs, the dump record and the warm-start state stay as they are, and all five may be called on one batch in any order.
+ * dwbc_batch_copy_kinematics does not copy the request.
+ * Refused (dwbc_last_error): DWBC_F32 batches, then a model without the kernel (built in for TOCABI's size on its own tree and on any;
+ * every kernel pack carries its size's), both at dwbc_batch_set_dynamics_outputs; an unknown bit -- the request and the outputs of the
+ * batch stay as they were; dwbc_batch_update_dynamics without a request; get / bind of an output that was not asked for;
+ * dwbc_batch_get_dynamics before the first launch of the request.
+ * Not built: fp32; the facade include/dwbc_amd.hpp, which keeps mirroring these members from its cycle; jac_com_ and the COM inertia (the
+ * link query's COM entry serves jac_com_); products such as A qddot + B; the reduced model's matrices; the link query in kernel packs. */
+enum dwbc_dynamics_output { DWBC_DYN_A = 0, DWBC_DYN_A_INV = 1, DWBC_DYN_B = 2, DWBC_DYN_G = 3, DWBC_DYN_CMM = 4, DWBC_DYN_COM = 5, DWBC_DYN_STATUS = 6 };
+/* mask: bits 1u << dwbc_dynamics_output; DWBC_DYN_STATUS is implied.  0 drops the request and its buffers.  A new request gets output
+ * buffers of its own: bound ones are let go of (bind again), earlier results are gone. */
+int dwbc_batch_set_dynamics_outputs(dwbc_batch *b, unsigned mask);
+/* asynchronous on the batch's stream; uploads newer host mirrors of q and qdot first, like a solve */
+int dwbc_batch_update_dynamics(dwbc_batch *b);
+size_t dwbc_batch_dynamics_bytes(const dwbc_batch *b, int what);  /* of all B instances; 0: not asked for, no such output */
+int dwbc_batch_get_dynamics(dwbc_batch *b, int what, void *host_out, size_t bytes);  /* synchronises the stream */
+/* zero-copy: a caller-owned DEVICE buffer of dwbc_batch_dynamics_bytes(b, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_dynamics(dwbc_batch *b, int what, void *device_ptr);
+/* name of the kernel dwbc_batch_update_dynamics launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b);
+/* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_dynamics(dwbc_batch *b, int steps, float *ms);
+
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least
  * squares), optional cost 1/2 y^T H y; levels are solved in sequence inside the null space of the earlier equalities.  The

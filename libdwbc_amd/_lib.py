@@ -109,6 +109,14 @@ SYMBOLS = [
     ("dwbc_batch_bind_grav", _i, [_vp, _i, _vp]),
     ("dwbc_batch_grav_kernel_name", C.c_char_p, [_vp]),
     ("dwbc_batch_time_grav", _i, [_vp, _i, C.POINTER(C.c_float)]),
+    # the dynamics half of UpdateKinematics (A_, A_inv_, B_, G_, CMM_, com_pos) in a launch of its own
+    ("dwbc_batch_set_dynamics_outputs", _i, [_vp, C.c_uint]),
+    ("dwbc_batch_update_dynamics", _i, [_vp]),
+    ("dwbc_batch_dynamics_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_batch_get_dynamics", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_bind_dynamics", _i, [_vp, _i, _vp]),
+    ("dwbc_batch_dynamics_kernel_name", C.c_char_p, [_vp]),
+    ("dwbc_batch_time_dynamics", _i, [_vp, _i, C.POINTER(C.c_float)]),
     # link poses, velocities and Jacobians in a launch of their own
     ("dwbc_batch_set_link_query", _i, [_vp, _i, _vp, _vp, _i]),
     ("dwbc_batch_update_kinematics", _i, [_vp]),

@@ -13,6 +13,8 @@
     wbc.grav_compensation(); wbc.grav_outputs()["tau"]       # CalcGravCompensation on its own; redistribute(add_gravity=True) adds it to the input
     wbc.set_link_query([0, 23], jacobians=True); wbc.update_kinematics()   # UpdateKinematics on its own: link_[i].xpos / rotm / v / w / jac_
     wbc.link_states()["rot"]
+    wbc.set_dynamics_outputs(["A", "B", "CMM"]); wbc.update_dynamics()   # the dynamics half of UpdateKinematics: rd_.A_ / A_inv_ / B_ / G_ / CMM_
+    wbc.dynamics()["A"]
 
 All arithmetic happens in libdwbc_hip.so (hand-written HIP, gfx950).  torch is only used, optionally, to own
 device buffers and streams (bind_tensor) and for torch.distributed in bench.py.
@@ -31,6 +33,7 @@ SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
 REDIST_ADD_GRAVITY = 8  # a bit of the redistribution entry points' flags
 GRAV_OUTPUTS = {"tau": 0, "wrench": 1, "status": 2}  # enum dwbc_grav_output
 LINK_QUERY_OUTPUTS = {"pos": 0, "rot": 1, "vel": 2, "jac": 3}  # enum dwbc_link_query_output
+DYNAMICS_OUTPUTS = {"A": 0, "A_inv": 1, "B": 2, "G": 3, "CMM": 4, "com": 5, "status": 6}  # enum dwbc_dynamics_output
 
 
 def describe(index, n, n_contacts, fstar_total, max_active):
@@ -517,6 +520,67 @@ class Batch:
         if not name:
             raise DwbcError(_lib.last_error())
         return name
+
+    # ---- the dynamics half of UpdateKinematics on its own: rd_.A_, A_inv_, B_, G_, CMM_, com_pos (reference src/dwbc.cpp:279-371)
+    def set_dynamics_outputs(self, names):
+        """The outputs update_dynamics() writes: any of "A" (n, n), "A_inv" (n, n), "B" (n), "G" (n), "CMM" (6, n), "com" (3); "status" is
+        always written.  What is not asked for is not computed: no "A_inv", no sweep; no "B", no RNEA; neither "CMM" nor "com", no centroidal
+        block.  An empty list drops the request and its buffers.  A new request has new output buffers: bind tensors after it."""
+        mask = 0
+        for k in names:
+            mask |= 1 << DYNAMICS_OUTPUTS[k]
+        _check(self._L.dwbc_batch_set_dynamics_outputs(self._h, mask))
+        for k in DYNAMICS_OUTPUTS:
+            self._keep.pop("dynamics_" + k, None)
+
+    def update_dynamics(self):
+        """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA and what the request asks for, from the state (and qdot, if
+        set_state got one; "B" is "G" to the bit otherwise).  Needs no contact and no task space, and leaves every output of solve(),
+        redistribute(), grav_compensation() and update_kinematics() as it is; the five may be called in any order."""
+        _check(self._L.dwbc_batch_update_dynamics(self._h))
+
+    def _dynamics_shape(self, name):
+        n = self.n
+        return {"A": ((self.B, n, n), np.float64), "A_inv": ((self.B, n, n), np.float64), "B": ((self.B, n), np.float64), "G": ((self.B, n), np.float64),
+                "CMM": ((self.B, 6, n), np.float64), "com": ((self.B, 3), np.float64), "status": ((self.B,), np.int32)}[name]
+
+    def dynamics(self):
+        """dict of the asked-for outputs and ``status`` (B,) int32 (0: "A_inv" was asked for and the sweep met a bad pivot; that instance's
+        outputs are zero) of the last update_dynamics(); synchronises the stream"""
+        out = {}
+        for name, what in DYNAMICS_OUTPUTS.items():
+            if self._L.dwbc_batch_dynamics_bytes(self._h, what) == 0 and name != "status":
+                continue
+            shape, dt = self._dynamics_shape(name)
+            a = np.zeros(shape, dt)
+            _check(self._L.dwbc_batch_get_dynamics(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def bind_dynamics(self, name, tensor):
+        """asked-for output ``name`` of update_dynamics() into a caller-owned device tensor (float64; "status": int32), written in place by
+        every later launch; None: back to a buffer of the batch's own"""
+        what = DYNAMICS_OUTPUTS[name]
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_dynamics(self._h, what, None))
+            self._keep.pop("dynamics_" + name, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = self._L.dwbc_batch_dynamics_bytes(self._h, what)
+        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(self._L.dwbc_batch_bind_dynamics(self._h, what, C.c_void_p(tensor.data_ptr())))
+        self._keep["dynamics_" + name] = tensor
+
+    def dynamics_kernel_name(self):
+        name = self._L.dwbc_batch_dynamics_kernel_name(self._h).decode()
+        if not name:
+            raise DwbcError(_lib.last_error())
+        return name
+
+    def time_dynamics(self, steps):
+        ms = C.c_float(0)
+        _check(self._L.dwbc_batch_time_dynamics(self._h, int(steps), C.byref(ms)))
+        return ms.value
 
     def time_solves(self, steps, reduced=False):
         ms = C.c_float(0)

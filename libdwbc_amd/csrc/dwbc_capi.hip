@@ -1189,4 +1189,145 @@ const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b) {
     return name;
 }
 
+// ---- the dynamics half of UpdateKinematics on its own (A_, A_inv_, B_, G_, CMM_, com_pos): the lean kernel of dwbc_dynamics.h
+static_assert(kDynA == 1u << DWBC_DYN_A && kDynAInv == 1u << DWBC_DYN_A_INV && kDynB == 1u << DWBC_DYN_B && kDynG == 1u << DWBC_DYN_G &&
+                  kDynCmm == 1u << DWBC_DYN_CMM && kDynCom == 1u << DWBC_DYN_COM, "DynIO::mask is 1u << dwbc_dynamics_output");
+static dwbc_plan::Plan dynamics_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.dynamics = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+
+// bytes of all B instances of one output under a request (0: not part of it, no such output)
+static size_t dynamics_bytes(const dwbc_batch *b, unsigned mask, int what) {
+    if (what < DWBC_DYN_A || what > DWBC_DYN_STATUS || !((mask >> what) & 1u)) return 0;
+    const size_t n = (size_t)b->n;
+    const size_t per[7] = {n * n * sizeof(double), n * n * sizeof(double), n * sizeof(double), n * sizeof(double), 6 * n * sizeof(double), 3 * sizeof(double), sizeof(int)};
+    return (size_t)b->B * per[what];
+}
+
+size_t dwbc_batch_dynamics_bytes(const dwbc_batch *b, int what) { return dynamics_bytes(b, b->dyn_mask, what); }
+
+int dwbc_batch_set_dynamics_outputs(dwbc_batch *b, unsigned mask) {
+    constexpr unsigned kAll = (1u << (DWBC_DYN_STATUS + 1)) - 1u;
+    if (mask & ~kAll) return fail("dynamics: unknown output bit (the outputs are 1u << DWBC_DYN_A .. 1u << DWBC_DYN_STATUS)");
+    if (mask) {
+        const dwbc_plan::Plan p = dynamics_plan(b);
+        if (!p.row) return fail(p.err);
+        mask |= 1u << DWBC_DYN_STATUS;
+    }
+    // outputs of the new request, owned by the batch; allocated here, so that dwbc_batch_update_dynamics itself allocates nothing
+    HIP_OK(hipSetDevice(b->device));
+    for (int w = DWBC_DYN_A; w <= DWBC_DYN_STATUS; w++) release(b->buf[fld::kDyA + w]);  // (hipFree waits for the launches that write them)
+    b->dyn_mask = mask;
+    b->dyn_ran = false;
+    for (int w = DWBC_DYN_A; w <= DWBC_DYN_STATUS; w++)
+        if (const size_t bytes = dwbc_batch_dynamics_bytes(b, w))
+            if (!ensure(b->buf[fld::kDyA + w], bytes)) return 0;
+    return 1;
+}
+
+static int launch_dynamics(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    const void *fn = p.row->fn;
+    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        b->lds_attr_set.push_back(fn);
+    }
+    BatchIO io{};  // the state and the model; no buffer of the cycle, the redistribution, the gravity compensation or the link query is named
+    io.B = b->B;
+    io.q = b->dev<double>(fld::kQ);
+    io.qdot = b->dev<double>(fld::kQdot);
+    io.body = b->d_body;
+    io.topo = b->d_topo;
+    io.pair_swap_bit = -1;
+    DynIO dio{};
+    dio.mask = b->dyn_mask & ~(1u << DWBC_DYN_STATUS);
+    dio.A = b->dev<double>(fld::kDyA);
+    dio.A_inv = b->dev<double>(fld::kDyAInv);
+    dio.Bv = b->dev<double>(fld::kDyB);
+    dio.G = b->dev<double>(fld::kDyG);
+    dio.CMM = b->dev<double>(fld::kDyCmm);
+    dio.com = b->dev<double>(fld::kDyCom);
+    dio.status = b->dev<int>(fld::kDyStatus);
+    void *args[] = {(void *)&b->su, (void *)&io, (void *)&dio};
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    b->dyn_ran = true;
+    return 1;
+}
+
+// uploads whatever is pending of the state, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+static int dynamics_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
+    if (!b->dyn_mask) return fail("no dynamics request: call dwbc_batch_set_dynamics_outputs first");
+    const dwbc_plan::Plan p = dynamics_plan(b);
+    if (!p.row) return fail(p.err);
+    HIP_OK(hipSetDevice(b->device));
+    bool queued = false;
+    for (const int slot : {fld::kQdot, fld::kQ})
+        if (!send(b, slot, &queued)) return 0;
+    if (queued && !mark_upload(b)) return 0;
+    if (planned) *planned = p;
+    return launch_dynamics(b, p);
+}
+
+int dwbc_batch_update_dynamics(dwbc_batch *b) { return dynamics_once(b, nullptr); }
+
+int dwbc_batch_time_dynamics(dwbc_batch *b, int steps, float *ms) {
+    HIP_OK(hipSetDevice(b->device));
+    dwbc_plan::Plan p{};
+    if (!dynamics_once(b, &p)) return 0;  // uploads + warm launch
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&]() -> int {
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, b->stream));
+        for (int i = 0; i < steps; i++)
+            if (!launch_dynamics(b, p)) return 0;
+        HIP_OK(hipEventRecord(e1, b->stream));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(ms, e0, e1));
+        return 1;
+    };
+    const int ok = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+
+// why output `what` of the request cannot be named (nullptr: it can)
+static const char *dynamics_refusal(const dwbc_batch *b, int what) {
+    if (what < DWBC_DYN_A || what > DWBC_DYN_STATUS) return "dynamics: unknown output";
+    if (!b->dyn_mask) return "no dynamics request: call dwbc_batch_set_dynamics_outputs first";
+    if (!((b->dyn_mask >> what) & 1u)) return "dynamics: this output was not asked for (dwbc_batch_set_dynamics_outputs)";
+    return nullptr;
+}
+
+int dwbc_batch_get_dynamics(dwbc_batch *b, int what, void *out, size_t bytes) {
+    if (const char *why = dynamics_refusal(b, what)) return fail(why);
+    if (!b->dyn_ran) return fail("no dynamics output yet: call dwbc_batch_update_dynamics first");
+    const size_t need = dwbc_batch_dynamics_bytes(b, what);
+    if (bytes < need) return fail("output buffer too small");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kDyA + what].d, out, need);
+}
+
+int dwbc_batch_bind_dynamics(dwbc_batch *b, int what, void *p) {
+    if (const char *why = dynamics_refusal(b, what)) return fail(why);
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kDyA + what];
+    release(u);
+    b->dyn_ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, dwbc_batch_dynamics_bytes(b, what));
+    u.d = p;
+    return 1;
+}
+
+const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = dynamics_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
+
 }  // extern "C"

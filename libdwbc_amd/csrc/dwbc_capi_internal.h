@@ -125,6 +125,10 @@ struct dwbc_batch {
     double lq_point[16][3] = {};
     bool lq_jac = false, lq_ran = false;
     bool gv_ran = false;  // a gravity-compensation launch (alone or ahead of a redistribution) has filled the DWBC_GRAV_* outputs
+    // the dynamics request (dwbc_batch_set_dynamics_outputs): bits 1u << dwbc_dynamics_output with DWBC_DYN_STATUS set (0: none), and
+    // whether a launch has filled the outputs
+    unsigned dyn_mask = 0;
+    bool dyn_ran = false;
     dwbc::DumpLayout dl{};
 };
 

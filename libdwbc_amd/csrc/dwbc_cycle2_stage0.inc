@@ -1,7 +1,7 @@
 // dwbc_cycle2_stage0.inc -- textual part of the fused cycle shared by cycle_instance_v2 (dwbc_cycle2.h) and
 // cycle_instance_reduced (dwbc_reduced.h): kinematics, CRBA, column-per-lane load of A and the A^-1 sweep.
 // Expects in scope: S (LDS map), N, NB, NT, th, su, io, L, body, topo, nb, qin, dump, dl, diag, s, dg.
-// Defines: st_contact.
+// Defines: st_contact.  With DWBC_STAGE0_FRONT_ONLY defined the text ends behind the column-per-lane load (dwbc_dynamics.h).
     // ================= stage 0: kinematics and CRBA (src/dwbc.cpp:279-371) =================
     for (int i = th.tid; i < N + 1; i += NT) L[S::q + i] = (real_t)qin[i];
     for (int i = th.tid; i < 3 * M; i += NT) L[S::tg + i] = real_t(0.0);
@@ -264,6 +264,7 @@
     }
     DWBC_STAMP(0);  // kinematics + CRBA done
     int st_contact = 1;
+#ifndef DWBC_STAGE0_FRONT_ONLY  // (dwbc_dynamics.h ends the text here: its A^-1 sweep is optional, and it stages no task reference)
     // A_inv (dwbc.cpp:307)
     if constexpr (std::is_same<Topo, TopoGeneric>::value) {
         // beyond 40 columns the runtime-pivot sweep would pick the lane's own pivot-row element from six candidate registers, which
@@ -315,3 +316,4 @@
         task_reference<S, N, NB, NT, kExtras>(th, su, io, inst, body, L, vel ? L + S::k_Rl : nullptr);
     }
     DWBC_STAMP(1);  // A_inv done
+#endif

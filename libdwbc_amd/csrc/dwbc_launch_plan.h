@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query or a gravity compensation):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation or the dynamics of UpdateKinematics):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -11,7 +11,8 @@ enum Arith { kDouble = 0, kFloat = 1 };
 // full-model cycle, reduced (centroidal) dynamics, general-contact cycle, redistribution of a caller-supplied torque (dwbc_redistribute.h),
 // link poses / velocities / Jacobians on their own (dwbc_link_query.h), gravity compensation alone or before such a redistribution
 // (dwbc_redistribute.h, GRAV = true)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5 };
+// the dynamics half of UpdateKinematics on its own (dwbc_dynamics.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -67,6 +68,9 @@ struct Request {
     // (dwbc_batch_grav_compensation, dwbc_batch_redistribute with DWBC_REDIST_ADD_GRAVITY); of the members above it reads the model, arith
     // and max_active (the caller plans the redistribution request as well where there is one: its refusals come first)
     bool grav_comp = false;
+    // not a cycle either: the dynamics half of UpdateKinematics on its own (dwbc_batch_update_dynamics); of the members above it reads the
+    // model and arith
+    bool dynamics = false;
 };
 
 struct Plan {
@@ -125,6 +129,14 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.arith == kFloat) return refuse("link query: fp64 batches only");
         const Row *r = Candidates(q, kLinkQuery, tabs, n_tabs).pick(0u, 0u);
         if (!r) return refuse("no link-query kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
+        return run(r, false);
+    }
+    // dynamics of UpdateKinematics: one kernel per model size and tree, whatever the batch size, the contact and task set-up or the cycle's
+    // options are (it reads the state alone)
+    if (q.dynamics) {
+        if (q.arith == kFloat) return refuse("dynamics: fp64 batches only");
+        const Row *r = Candidates(q, kDynamics, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no dynamics kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         return run(r, false);
     }
     // gravity compensation: planned like the redistribution below, whatever the batch size, the levels or the cycle's options are
