@@ -490,7 +490,13 @@ DWBC_WDEV void lds_rows_axpy(const real_t *A, const real_t (&x)[NR], real_t (&ac
 }
 
 #if !defined(DWBC_HOST_EMU)
-template <int NN, int K, int LO = 0>
+// OWN: the pivot lane scales its OWN copy of the pivot column by 1/d instead of forming own - other (1 - 1/d) from the gathered one.
+// The gathered column holds the other lanes' copies of the symmetric entries; the two copies of an entry whose row was pivoted
+// earlier differ by that pivot's cancellation error, u |A_ij|, which the difference passes on undivided (g = 195 where the
+// register sweep has 1 on a matrix with pivots near 1e3: tests/test_wave_probe_gpu.py::test_spd_inverse_reg[spd_reg39_lds]).
+// NN more multiplies per pivot: taken by spd_inverse_reg (dwbc_cycle_gc.h), not by the product kernels, whose matrices have
+// pivots of order 1 .. 1e2 and whose answers sit far above u |A|max.
+template <int NN, int K, int LO = 0, bool OWN = false>
 __device__ __forceinline__ void lds_pivot(double (&s)[NN], double &dg2, int &ok, unsigned cb, int lane) {
     constexpr int NP = (NN + 1) / 2;
     dwbc_d2v col[NP];
@@ -503,15 +509,22 @@ __device__ __forceinline__ void lds_pivot(double (&s)[NN], double &dg2, int &ok,
     if (!(d > 0.0)) d = 1.0;
     const double rp = fast_rcp(d);
     const double cj = s[K];     // pivot lane: d - 1
-    const double h = cj * rp;   // pivot lane: 1 - 1/d, the multiplier of the pivot column itself
+    double h = cj * rp;         // pivot lane: 1 - 1/d, the multiplier of the pivot column itself
+    if constexpr (OWN) h = (lane == K + LO) ? 0.0 : h;
     lds_col_wait<NP>(col);
 #pragma unroll
     for (int i = 0; i < NN; i++) s[i] -= col[i / 2][i & 1] * h;
+    if constexpr (OWN) {
+        if (lane == K + LO) {
+#pragma unroll
+            for (int i = 0; i < NN; i++) s[i] *= rp;
+        }
+    }
     // pivot lane: -1/d.  Taken from rp, not from (d - 2) - (d - 1)^2 / d: that difference of two numbers of size d carries an error of
     // u d on a result of size 1/d (tests/wave_cases.py, the synthetic tree matrix with pivots near 1e3: 6.7e4 u kappa off where the
     // register sweep is 0.9 off)
     dg2 = (lane == K + LO) ? -rp : dg2 - cj * h;
-    if constexpr (K > 0) lds_pivot<NN, K - 1, LO>(s, dg2, ok, cb, lane);
+    if constexpr (K > 0) lds_pivot<NN, K - 1, LO, OWN>(s, dg2, ok, cb, lane);
 }
 #endif
 
@@ -763,7 +776,7 @@ DWBC_WDEV int sweep_inverse_tree_lds(PLA_REF(real_t, s, NN), PL_REF(real_t, dg),
 }
 
 // LO: lane of matrix column 0 (the columns sit in lanes LO .. LO + NN - 1; colbuf: 64 doubles)
-template <int NN, int LO = 0>
+template <int NN, int LO = 0, bool OWN = false>
 DWBC_WDEV int sweep_inverse_lds(PLA_REF(real_t, s, NN), PL_REF(real_t, dg), real_t *colbuf) {
 #if defined(DWBC_HOST_EMU)
     (void)colbuf;
@@ -780,7 +793,7 @@ DWBC_WDEV int sweep_inverse_lds(PLA_REF(real_t, s, NN), PL_REF(real_t, dg), real
             for (int i = 0; i < NN; i++) s[i] = (i == lp - LO) ? dg - 1.0 : s[i];
         }
         double dg2 = dg - 2.0;
-        lds_pivot<NN, NN - 1, LO>(s, dg2, ok, (unsigned)(size_t)colbuf, lane);
+        lds_pivot<NN, NN - 1, LO, OWN>(s, dg2, ok, (unsigned)(size_t)colbuf, lane);
         ok = DWBC_FLAG_UNIFORM(ok);
         {
             DWBC_LANE_OPAQUE(le);
@@ -1033,10 +1046,15 @@ DWBC_DEVN void qr_small(Thr th, real_t *A, int m, int n, real_t *Q, real_t *piv,
 // COD_THRESHOLD = 1e-6, include/dwbc_wbd.h:10; restated in oracle/dwbc_oracle.c orc_pinv_cod).  Called only for a block the SPD
 // factorisation found ill-conditioned (a nearly straight knee makes Q W^+ Q^T of a pelvis level lose a direction): a full-rank
 // verdict leaves the caller's SPD inverse in place (returns t), a truncated one writes pinv(M_r) = P R1^+ Q1^T into Out.
-//   Mr: the block (t x t, row stride t), destroyed.  Qm, Gm, Tm: t x t scratch each, vec: 3 t reals.
-template <int NT>
+//   Mr: the block (t x t, row stride t), destroyed.  Qm, Gm, Tm: t x t scratch each.  TMAX: the caller's compile-time bound of t.
+//   vec: 3 TMAX reals -- vec[0 .. t-1] the column permutation of the first QR (read by the final scatter), vec[TMAX .. TMAX+rank-1]
+//   the identity permutation the second, unpivoted QR writes and nobody reads; the third TMAX is spare.  (The second list sat at
+//   vec + 6 whatever the bound: for t > 6 it overwrote piv[6 ..] and the scatter wrote the wrong rows -- the general-contact kernel's
+//   TG = 12 build; tests/test_wave_probe_*.py::test_pinv_cod.  A compile-time offset keeps the product kernels' code as it was.)
+template <int NT, int TMAX = kMaxTaskDof>
 DWBC_DEVN int pinv_cod_small(Thr th, real_t *Mr, int t, real_t thr, real_t *Out, real_t *Qm, real_t *Gm, real_t *Tm, real_t *vec) {
-    real_t *piv = vec, *pz = vec + 6;
+    static_assert(TMAX >= kMaxTaskDof && TMAX <= kMaxTaskDofWide, "qr_small's reflector holds kMaxTaskDofWide entries");
+    real_t *piv = vec, *pz = vec + TMAX;
     qr_small<NT>(th, Mr, t, t, Qm, piv, true);
     real_t maxp = real_t(0.0);
     for (int i = 0; i < t; i++) { const real_t a = fabs(Mr[i * t + i]); maxp = a > maxp ? a : maxp; }

@@ -118,6 +118,7 @@ struct LdsG {
     static constexpr int t_s3 = t_s2 + T * T;         // T x T
     static constexpr int t_cod = t_s3 + T * T;        // scratch of pinv_cod_small: 3 x (T x T) + 3 T
     static constexpr int t_base = t_cod + 3 * T * T + 3 * T;  // M
+    static_assert(t_base - (t_cod + 3 * T * T) >= 3 * T, "vec of pinv_cod_small<NT, T>: piv at vec[0 .. t-1], the second list at vec[T .. T+rank-1] (t <= T)");
     static constexpr int t_F = t_base + M;            // C x T
     static constexpr int t_fv = t_F + C * T;          // C
     static constexpr int qp_V = t_fv + C;             // QN
@@ -149,7 +150,7 @@ DWBC_DEVN int spd_inverse_reg(const real_t *Sin, int ld, real_t *Out, int ldo, r
         LV(dg) = (lane < NN) ? Sin[col * ld + col] : real_t(1.0);
     }
     DWBC_SYNC();
-    const int ok = colbuf ? sweep_inverse_lds<NN>(s, dg, colbuf) : sweep_inverse_rl<NN>(s, dg, NN);
+    const int ok = colbuf ? sweep_inverse_lds<NN, 0, true>(s, dg, colbuf) : sweep_inverse_rl<NN>(s, dg, NN);  // (true: the pivot lane's own column, see lds_pivot)
 #if !defined(DWBC_HOST_EMU)
 #pragma unroll
     for (int i = 0; i < NN; i++) asm volatile("" : "+v"(s[i]));  // (the stores below are conditional: see sweep_inverse_tree_lds, dwbc_cycle2.h)
@@ -640,7 +641,7 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
             const real_t piv = gj_inverse_rows<T, NT>(th, L + S::t_s2, t, t, L + S::t_s3, t, L + S::t_s1);
             if (!(piv > kCodCheck)) {
                 real_t *cod = L + S::t_cod;
-                pinv_cod_small<NT>(th, L + S::t_s2, t, kCodThreshold, L + S::t_s3, cod, cod + T * T, cod + 2 * T * T, cod + 3 * T * T);
+                pinv_cod_small<NT, T>(th, L + S::t_s2, t, kCodThreshold, L + S::t_s3, cod, cod + T * T, cod + 2 * T * T, cod + 3 * T * T);
                 DWBC_SYNC();
             }
             mmg<M, T, T, 2>(Jkt, t, QW, M, L + S::t_s3, t, M, t, t);     // J_kt = W^+ Q^T pinv(.)

@@ -15,12 +15,16 @@ BUILD = "emu"
 def test_instantiation_table_holds_every_family():
     t = probe.table(BUILD)
     names = ["lanes", "lanes_f32", "math", "math_f32"] + [g[0] for g in wc.GEMM_INSTS] + list(wc.DOT_INSTS) + list(wc.AXPY_INSTS)
-    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS)
+    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS)
     assert sorted(t) == sorted(names)
 
 
 def test_entry_refuses_out_of_range_sizes():
     wc.check_lanes_refusals(BUILD)
+
+
+def test_general_contact_routines_refuse_out_of_range_sizes():
+    wc.check_gc_refusals(BUILD)
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
@@ -60,6 +64,32 @@ def test_lds_rows_axpy(name):
 @pytest.mark.parametrize("name", list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS))
 def test_inverse(name):
     wc.check_inverse(BUILD, name)
+
+
+@pytest.mark.parametrize("t", wc.PINV_TS)
+def test_pinv_cod(t):
+    """pinv_cod_small / qr_small at every (t, rank).  With the second permutation list at vec + 6 (before it moved to vec + t) the
+    cases of t >= 7 failed here -- |M P M - M| up to 1e4 -- and those of t <= 6 passed: the test fails where that bug was and only there"""
+    wc.check_pinv_cod(BUILD, (t,))
+
+
+@pytest.mark.parametrize("name", list(wc.GJ_INSTS))
+def test_gj_inverse_rows(name):
+    wc.check_gj_rows(BUILD, name)
+
+
+@pytest.mark.parametrize("name", list(wc.SPD_REG_INSTS))
+def test_spd_inverse_reg(name):
+    wc.check_spd_reg(BUILD, name)
+
+
+def test_spd_inverse_scaled():
+    wc.check_spd_scaled(BUILD)
+
+
+@pytest.mark.parametrize("name", list(wc.MMG_INSTS))
+def test_mmg(name):
+    wc.check_mmg(BUILD, name)
 
 
 def test_committed_tolerances_are_the_host_figures(tmp_path):

@@ -1,6 +1,7 @@
 """-m gpu: the wave-routine probe (tests/wave_probe) in its DEVICE build -- the bodies that ship behind the DWBC_HOST_EMU forks (DPP
 reductions and scans, v_readlane broadcasts, fast_rcp / fast_rsqrt / sincos_r, wave_gemm on the matrix cores, the LDS-fed sweeps,
-spd_inverse12_lds, the three-group Cholesky inverse, the hand-batched row products), each alone on the cases and against the 50-digit
+spd_inverse12_lds, the three-group Cholesky inverse, the hand-batched row products, and the general-contact kernel's pinv_cod_small,
+gj_inverse_rows, spd_inverse_reg, spd_inverse_scaled and mmg), each alone on the cases and against the 50-digit
 references of tests/wave_cases.py, with 64 and with 128 threads per block (the two-wave kernel runs them in wave 1).  One launch per
 instantiation.  The host twin, which validates the same cases and references, is tests/test_wave_probe_emu.py."""
 import pytest
@@ -15,12 +16,16 @@ THREADS = pytest.mark.parametrize("threads", [64, 128])
 
 def test_instantiation_table_holds_every_family():
     names = ["lanes", "lanes_f32", "math", "math_f32"] + [g[0] for g in wc.GEMM_INSTS] + list(wc.DOT_INSTS) + list(wc.AXPY_INSTS)
-    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS)
+    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS)
     assert sorted(probe.table(BUILD)) == sorted(names)
 
 
 def test_entry_refuses_out_of_range_sizes():
     wc.check_lanes_refusals(BUILD)
+
+
+def test_general_contact_routines_refuse_out_of_range_sizes():
+    wc.check_gc_refusals(BUILD)
 
 
 @THREADS
@@ -68,3 +73,37 @@ def test_lds_rows_axpy(name, threads):
 @pytest.mark.parametrize("name", list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS))
 def test_inverse(name, threads):
     wc.check_inverse(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("t", wc.PINV_TS)
+def test_pinv_cod(t, threads):
+    """pinv_cod_small / qr_small at every (t, rank): t > 6 is the general-contact kernel's TG = 12 build"""
+    wc.check_pinv_cod(BUILD, (t,), threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.GJ_INSTS))
+def test_gj_inverse_rows(name, threads):
+    wc.check_gj_rows(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.SPD_REG_INSTS))
+def test_spd_inverse_reg(name, threads):
+    """spd_inverse_reg in place through both feeds.  spd_reg39_lds is the case that found the pivot-lane defect of the LDS-fed sweep
+    (lds_pivot, dwbc_cycle2.h): with the pivot lane forming own - other (1 - 1/d) from the gathered column it scored g = 194.8
+    against the bar of 12.25 on the synthetic matrix with pivots near 1e3 (errors in X[i][j], i > j, only: u |A_ij| undivided);
+    spd_inverse_reg now has the pivot lane scale its own copy."""
+    wc.check_spd_reg(BUILD, name, threads)
+
+
+@THREADS
+def test_spd_inverse_scaled(threads):
+    wc.check_spd_scaled(BUILD, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.MMG_INSTS))
+def test_mmg(name, threads):
+    wc.check_mmg(BUILD, name, threads)

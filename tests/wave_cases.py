@@ -1,5 +1,7 @@
 """Cases, 50-digit mpmath references and checks of the wave-routine probe (tests/wave_probe): the device-only bodies behind the
-DWBC_HOST_EMU forks -- cross-lane primitives, scalar math, wave_gemm, the inverses and the batched row products -- each alone.
+DWBC_HOST_EMU forks -- cross-lane primitives, scalar math, wave_gemm, the inverses and the batched row products -- and the routines
+of the general-contact kernel (section 6: the rank-revealing pseudo-inverse, the pivoted Gauss-Jordan inverse, the register-sweep
+inverses, the run-time sized matrix-core product), each alone.
 
 Both builds of the probe run the same cases against the same references: tests/test_wave_probe_emu.py (host emulation: validates the
 cases and the references, and is where the bars of the inverses come from) and tests/test_wave_probe_gpu.py (the device bodies).
@@ -734,6 +736,444 @@ def check_small(build, name, threads=64, bar=None):
     return dict(worst_g=worst, worst_sym=worst_sym, n=len(cs), ok=oks)
 
 
+# ====================================================================================================================================
+# 6. the routines of the general-contact kernel: pinv_cod_small / qr_small, gj_inverse_rows, spd_inverse_reg, spd_inverse_scaled, mmg
+# ====================================================================================================================================
+COD_THR = 1.0e-6  # kCodThreshold of the fp64 build (dwbc_cycle.h), COD_THRESHOLD of the reference
+COD_CHECK = 1.0e-4  # kCodCheck
+PINV_TS = tuple(range(1, 13))
+GJ_INSTS = {"gj_rows6": 6, "gj_rows12": 12, "gj_rows18": 18}
+SPD_REG_INSTS = {"spd_reg39_lds": 39, "spd_reg33_lds": 33, "spd_reg33_rl": 33}
+# name: MAXM, MAXN, MAXK, OP -- the bounds of the TG = 12 kernel's calls (dwbc_cycle_gc.h stage 3)
+MMG_INSTS = {"mmg_12_39_39_nn": (12, 39, 39, 0), "mmg_12_12_39_nt": (12, 12, 39, 1), "mmg_33_12_12_tn": (33, 12, 12, 2),
+             "mmg_12_33_12_nn": (12, 33, 12, 0)}
+GC_INVERSE_INSTS = ("pinv_cod12",) + tuple(GJ_INSTS) + tuple(SPD_REG_INSTS) + ("spd_scaled12",)
+
+
+def _mpm(A):
+    return [[mpf(float(v)) for v in r] for r in np.atleast_2d(A)]
+
+
+def _mp_qrcp(A):
+    """Householder QR with column pivoting in 50 digits: the largest remaining column norm first (the first of equal ones), reflector
+    sign against the pivot.  A (nested lists of mpf) = Q R Pi^T; returns Q, R, piv (piv[j] = the original column in position j) and,
+    per step, the ratio of the largest to the second largest remaining column norm"""
+    m, n = len(A), len(A[0])
+    R = [r[:] for r in A]
+    Q = [[mpf(1) if i == j else mpf(0) for j in range(m)] for i in range(m)]
+    piv = list(range(n))
+    gaps = []
+    for s in range(min(m, n)):
+        nr = [sum(R[i][j] ** 2 for i in range(s, m)) for j in range(s, n)]
+        order = sorted(range(len(nr)), key=lambda j: (-nr[j], j))
+        best = s + order[0]
+        if len(nr) > 1:
+            gaps.append(mp.sqrt(nr[order[0]] / nr[order[1]]) if nr[order[1]] > 0 else mp.inf)
+        if best != s:
+            for i in range(m):
+                R[i][s], R[i][best] = R[i][best], R[i][s]
+            piv[s], piv[best] = piv[best], piv[s]
+        v = [R[i][s] for i in range(s, m)]
+        nrm = mp.sqrt(sum(x * x for x in v))
+        if nrm == 0:
+            continue
+        v[0] -= -nrm if v[0] > 0 else nrm
+        vn = sum(x * x for x in v)
+        if vn == 0:
+            continue
+        beta = 2 / vn
+        for j in range(s, n):
+            d = beta * sum(v[i - s] * R[i][j] for i in range(s, m))
+            for i in range(s, m):
+                R[i][j] -= d * v[i - s]
+        for i in range(m):
+            d = beta * sum(Q[i][k] * v[k - s] for k in range(s, m))
+            for k in range(s, m):
+                Q[i][k] -= d * v[k - s]
+    return Q, R, piv, gaps
+
+
+def _mp_pinv_cod(M, thr=COD_THR):
+    """the reference's rule (PinvCODWB, src/wbd.cpp:5-30) restated in 50 digits: column-pivoted Householder QR, rank = #{|R_ii| > thr
+    max |R_ii|}, the pseudo-inverse of the kept rows R1 = R[:rank] permuted back: P = Pi R1^+ Q1^T.  NOT an SVD truncation (the two
+    differ at O(dropped pivot / kept pivot)).  Returns P (object array of mpf), rank, room (the factor by which the closest |R_ii|
+    clears thr max |R_ii|, on its side) and the pivot gaps of _mp_qrcp"""
+    t = M.shape[0]
+    Q, R, piv, gaps = _mp_qrcp(_mpm(M))
+    d = [abs(R[i][i]) for i in range(t)]
+    bar = mpf(thr) * max(d)
+    rank = sum(1 for x in d if x > bar)
+    room = min([mp.inf] + [(x / bar if x > bar else (bar / x if x > 0 else mp.inf)) for x in d if bar > 0])
+    assert all(d[i] > bar for i in range(rank)), "the kept pivots lead"
+    P = np.array([[mpf(0)] * t for _ in range(t)], dtype=object)
+    if rank > 0:
+        R1 = mp.matrix(R[:rank])
+        R1p = R1.T * mp.inverse(R1 * R1.T)  # t x rank: the minimum-norm solution operator of the kept rows
+        for i in range(t):
+            for j in range(t):
+                P[piv[i], j] = sum(R1p[i, k] * Q[j][k] for k in range(rank))
+    return P, rank, float(room), [float(g) for g in gaps]
+
+
+def _orth(rng, t, r):
+    Q, _ = np.linalg.qr(rng.standard_normal((t, t)))
+    return Q[:, :r]
+
+
+@functools.lru_cache(maxsize=None)
+def pinv_cases(t):
+    """(kind, M, rank or None).  deficient: M = F diag(s) F^T with t x rank orthonormal F, s within a factor 4, at three overall scales
+    (the rule is relative); zero; full (SPD: the verdict leaves the caller's inverse alone); nonsym: F1 diag(s) F2^T (t = 7 and 12);
+    thr_kept / thr_dropped: M = Q R with the smallest pivot at 1e-5 / 1e-7 of the largest and column norms a factor >= 1.3 apart"""
+    rng = np.random.default_rng(6000 + t)
+    cs = []
+    for r in range(1, t):
+        for scale in (1.0e-3, 1.0, 1.0e3):
+            F = _orth(rng, t, r)
+            M = (F * (scale * rng.uniform(1.0, 4.0, r))) @ F.T
+            cs.append(("deficient", 0.5 * (M + M.T), r))
+    cs.append(("zero", np.zeros((t, t)), 0))
+    cs.append(("full", _spd(rng, t), t))
+    if t in (7, 12):
+        for r in (t - 3, 2):
+            cs.append(("nonsym", (_orth(rng, t, r) * rng.uniform(1.0, 4.0, r)) @ _orth(rng, t, r).T, r))
+    if t >= 2:
+        for kind, last in (("thr_kept", 1.0e-5), ("thr_dropped", 1.0e-7)):
+            d = np.concatenate([np.geomspace(1.0, 1.0e-2, t - 1), [last]]) if t > 2 else np.array([1.0, last])
+            if t > 2:
+                assert (d[:-1] / d[1:]).min() >= 1.3
+            R = np.diag(d) + np.triu(rng.uniform(-1.0, 1.0, (t, t)), 1) * d[None, :] * (0.3 / np.sqrt(t))
+            cs.append((kind, _orth(rng, t, t) @ R, t if kind == "thr_kept" else t - 1))
+    return cs
+
+
+@functools.lru_cache(maxsize=None)
+def _pinv_ref(t):
+    """per case (P_mp, rank, kappa_r); asserts of the CASES: the rank the case was built for, a factor 10 of room in every rank
+    decision, a 10 % gap of the column norms wherever the pivot order matters (a dropped pivot that is not round-off), and that the
+    reference rounded to double scores g <= 1"""
+    out = []
+    for kind, M, rank in pinv_cases(t):
+        P, rk, room, gaps = _mp_pinv_cod(M)
+        assert rk == rank, (t, kind, rk, rank)
+        assert room >= 9.99, (t, kind, "room of the rank decision", room)  # (the threshold pairs sit AT the factor 10, up to the rounding of M)
+        if kind.startswith("thr"):
+            assert min(gaps) >= 1.1, (t, kind, "pivot order", gaps)
+        sv = np.linalg.svd(M, compute_uv=False)
+        kappa = float(sv[0] / sv[rank - 1]) if rank > 0 else 1.0
+        if 0 < rank < t:
+            assert _gfig(_f(P), P, kappa)[0] <= 1.0
+        out.append((P, rk, kappa))
+    return out
+
+
+def check_pinv_cod(build, ts=PINV_TS, threads=64, bar=None):
+    """pinv_cod_small at t = ts, one launch per t.  Asserts: the rank of the 50-digit rule; g = |P - P_mp|max / (u kappa_r |P_mp|max),
+    kappa_r over the KEPT singular values; on the exactly deficient cases both Penrose identities, independent of the restated rule:
+    with P = M^+ + E, |E| <= bar u kappa_r |P|max, M P M - M = M E M and P M P - P = E M P + P M E to first order, |M|max |P|max <=
+    kappa_r, so t^2 bar u kappa_r^2 |M|max and 2 t^2 bar u kappa_r^2 |P|max bound them (+ 4 t u kappa_r |.|max for the round-off
+    the deficient directions of M itself carry)"""
+    bar = inverse_bar("pinv_cod12") if bar is None else bar
+    worst = worst_pen = 0.0
+    ncase = 0
+    for t in ts:
+        cs, ref = pinv_cases(t), _pinv_ref(t)
+        din = np.full((len(cs), 144), np.nan)
+        for b, (kind, M, rank) in enumerate(cs):
+            din[b, :t * t] = M.ravel()
+        o = probe.run(build, "pinv_cod12", din, np.full((len(cs), 1), t), threads)
+        ncase += len(cs)
+        for b, (kind, M, rank) in enumerate(cs):
+            tag = f"{build} pinv_cod12 t{threads} t = {t} case {b} ({kind}, rank {rank})"
+            Pm, rk, kappa = ref[b]
+            assert np.isnan(o[b, 145:]).all(), (tag, "written behind vec")
+            assert (o[b, t * t:144] == probe.FRAME_SENTINEL).all(), (tag, "written beyond t x t")
+            assert o[b, 144] == rk, (tag, "rank", o[b, 144], rk)
+            P = o[b, :t * t].reshape(t, t)
+            if rk == t:
+                assert (P == probe.FRAME_SENTINEL).all(), (tag, "a full-rank verdict leaves Out alone")
+                continue
+            if rk == 0:
+                assert (P == 0.0).all(), tag
+                continue
+            assert np.isfinite(P).all(), tag
+            g, nrm = _gfig(P, Pm, kappa)
+            worst = max(worst, g)
+            assert g <= bar, (tag, "g", g, bar)
+            if kind in ("deficient", "nonsym"):
+                Ml, Pl = M.astype(np.longdouble), P.astype(np.longdouble)
+                p1 = float(np.abs(Ml @ Pl @ Ml - Ml).max()) / (U64 * np.abs(M).max())
+                p2 = float(np.abs(Pl @ Ml @ Pl - Pl).max()) / (U64 * np.abs(P).max())
+                b1, b2 = t * t * bar * kappa ** 2 + 4 * t * kappa, 2 * t * t * bar * kappa ** 2 + 4 * t * kappa
+                worst_pen = max(worst_pen, p1 / b1, p2 / b2)
+                assert p1 <= b1 and p2 <= b2, (tag, "Penrose", p1, b1, p2, b2)
+    return dict(worst_g=worst, worst_sym=0.0, worst_penrose=worst_pen, n=ncase)
+
+
+def _mp_gj_pivots(A, first=None):
+    """Gauss-Jordan with partial pivoting in 50 digits (the largest remaining element of the column; `first`: the row forced at column
+    0): the pivot magnitudes, and the smallest ratio of the largest to the second largest candidate over the unforced steps"""
+    n = A.shape[0]
+    R = _mpm(A)
+    free = list(range(n))
+    pivs, margin = [], mp.inf
+    for c in range(n):
+        cand = sorted(((abs(R[i][c]), -i) for i in free), reverse=True)
+        p = -cand[0][1]
+        if c == 0 and first is not None:
+            p = first
+        elif len(cand) > 1 and cand[0][0] > 0:
+            margin = min(margin, cand[0][0] / cand[1][0] if cand[1][0] > 0 else mp.inf)
+        pivs.append(abs(R[p][c]))
+        free.remove(p)
+        if R[p][c] == 0:
+            return pivs, mpf(0)
+        for i in free:
+            f = R[i][c] / R[p][c]
+            for j in range(c, n):
+                R[i][j] -= f * R[p][j]
+    return pivs, margin
+
+
+@functools.lru_cache(maxsize=None)
+def gj_cases(NMAX):
+    """(kind, n, A, extra): general, NON-symmetric matrices, each run out of place and in place.  random (every n); zero_lead (A[0][0] =
+    0) and zero_diag (pivoting is needed from the first column on); permdiag (a permutation times a diagonal over 1e-6 .. 1e6); tie
+    (the two largest entries of column 0 agree in all but the 7 lowest mantissa bits, which the device's arg-min drops: either row is
+    a valid pivot; extra = the two rows); singular (two equal rows)"""
+    rng = np.random.default_rng(6100 + NMAX)
+    cs = []
+    for n in range(1, NMAX + 1):
+        cs.append(("random", n, rng.standard_normal((n, n)) + 2.0 * np.eye(n)[rng.permutation(n)], None))
+    Z = rng.standard_normal((NMAX, NMAX))
+    Z[0, 0] = 0.0
+    cs.append(("zero_lead", NMAX, Z, None))
+    Z = rng.standard_normal((NMAX, NMAX)) + 3.0 * np.eye(NMAX)[np.roll(np.arange(NMAX), 1)]
+    Z[np.diag_indices(NMAX)] = 0.0
+    cs.append(("zero_diag", NMAX, Z, None))
+    cs.append(("permdiag", NMAX, np.eye(NMAX)[rng.permutation(NMAX)] * np.geomspace(1.0e-6, 1.0e6, NMAX)[rng.permutation(NMAX)], None))
+    for k in range(4):
+        A = rng.standard_normal((NMAX, NMAX)) + 2.0 * np.eye(NMAX)
+        A[:, 0] = np.clip(A[:, 0], -1.5, 1.5)
+        i, j = sorted(int(v) for v in rng.choice(NMAX, 2, replace=False))
+        base = np.float64(rng.uniform(3.0, 4.0)).view(np.uint64) & ~np.uint64(127)
+        lo = rng.choice(128, 2, replace=False).astype(np.uint64)
+        A[i, 0], A[j, 0] = (base | lo[0]).view(np.float64), (base | lo[1]).view(np.float64) * (-1.0 if k % 2 else 1.0)
+        cs.append(("tie", NMAX, A, (i, j)))
+    n = NMAX // 2 + 2
+    S = rng.standard_normal((n, n))
+    S[n - 2] = S[1]
+    cs.append(("singular", n, S, None))
+    return cs
+
+
+@functools.lru_cache(maxsize=None)
+def _gj_ref(NMAX):
+    """per case (X_mp, kappa, the valid pivot ratios, whether the pivot order is unambiguous)"""
+    out = []
+    for kind, n, A, extra in gj_cases(NMAX):
+        if kind == "singular":
+            pivs, _ = _mp_gj_pivots(A)
+            assert min(pivs) == 0
+            out.append(None)
+            continue
+        Xm, kappa = _mp_inverse(A), float(np.linalg.cond(A))
+        assert _gfig(_f(Xm), Xm, kappa)[0] <= 1.0
+        ratios, clear = [], False
+        for first in (extra if kind == "tie" else (None,)):
+            pivs, margin = _mp_gj_pivots(A, first)
+            ratios.append(float(min(pivs) / max(pivs)))
+            clear = kind != "tie" and margin >= 1.0 + 1.0e-6
+            if kind == "tie":
+                assert margin >= 1.0 + 1.0e-6, "the tie is the only ambiguous pivot"
+        out.append((Xm, kappa, ratios, clear))
+    return out
+
+
+def check_gj_rows(build, name, threads=64, bar=None):
+    """gj_inverse_rows<NMAX>: g against the 50-digit inverse; the returned pivot ratio against the pivots of the 50-digit elimination to
+    1e-10 relative where the pivot order is unambiguous, within 2^-45 of one of the two valid values on the tie cases; nothing written
+    outside n x n; the singular case returns a ratio below kCodCheck (values not asserted)"""
+    NMAX = GJ_INSTS[name]
+    cs, ref = gj_cases(NMAX), _gj_ref(NMAX)
+    bar = inverse_bar(name) if bar is None else bar
+    din = np.full((2 * len(cs), NMAX * NMAX), np.nan)
+    ip = np.zeros((2 * len(cs), 2), np.int32)
+    for b, (kind, n, A, extra) in enumerate(cs):
+        for inplace in (0, 1):
+            din[2 * b + inplace, :n * n] = A.ravel()
+            ip[2 * b + inplace] = (n, inplace)
+    o = probe.run(build, name, din, ip, threads)
+    worst = worst_ratio = 0.0
+    for b, (kind, n, A, extra) in enumerate(cs):
+        for inplace in (0, 1):
+            tag = f"{build} {name} t{threads} case {b} ({kind}, n = {n}, {'in place' if inplace else 'out of place'})"
+            r = o[2 * b + inplace]
+            rest = r[n * n:NMAX * NMAX]
+            assert (np.isnan(rest).all() if inplace else (rest == probe.FRAME_SENTINEL).all()), (tag, "written beyond n x n")
+            ratio = r[NMAX * NMAX]
+            if ref[b] is None:
+                assert 0.0 <= ratio < COD_CHECK, (tag, "pivot ratio of a singular matrix", ratio)
+                continue
+            Xm, kappa, ratios, clear = ref[b]
+            X = r[:n * n].reshape(n, n)
+            assert np.isfinite(X).all(), tag
+            g, _ = _gfig(X, Xm, kappa)
+            worst = max(worst, g)
+            assert g <= bar, (tag, "g", g, bar)
+            rel = min(abs(ratio - v) / v for v in ratios)
+            if kind == "tie":
+                assert rel <= 2.0 ** -45, (tag, "pivot ratio", ratio, ratios)
+            elif clear:
+                worst_ratio = max(worst_ratio, rel)
+                assert rel <= 1.0e-10, (tag, "pivot ratio", ratio, ratios)
+    return dict(worst_g=worst, worst_sym=0.0, worst_ratio=worst_ratio, n=len(cs))
+
+
+def check_spd_reg(build, name, threads=64, bar=None):
+    """spd_inverse_reg<NN> in place on sweep_cases(NN) without the riding columns, checked as check_sweep does"""
+    NN = SPD_REG_INSTS[name]
+    cs, ref = sweep_cases(NN), _sweep_ref(NN)
+    bar = inverse_bar(name) if bar is None else bar
+    o = probe.run(build, name, np.stack([A.ravel() for _, A, _ in cs]), None, threads)
+    worst = worst_sym = 0.0
+    for b, (kind, A, _) in enumerate(cs):
+        tag = f"{build} {name} t{threads} case {b} ({kind})"
+        ok = o[b, NN * NN]
+        if kind == "indefinite":
+            assert ok == 0, (tag, "ok", ok)
+            continue
+        assert ok == 1, (tag, "ok", ok)
+        Xm, _, kappa = ref[b]
+        X = o[b, :NN * NN].reshape(NN, NN)
+        assert np.isfinite(X).all(), tag
+        g, nrm = _gfig(X, Xm, kappa)
+        sym = float(np.abs(X - X.T).max())
+        worst, worst_sym = max(worst, g), max(worst_sym, sym / (U64 * kappa * nrm))
+        assert g <= bar, (tag, "g", g, bar)
+        assert sym <= 2.0 * bar * U64 * kappa * nrm, (tag, "|X - X^T|", sym)
+    return dict(worst_g=worst, worst_sym=worst_sym, n=len(cs))
+
+
+def check_spd_scaled(build, threads=64, bar=None):
+    """spd_inverse_scaled<12> in place on the cases of spd_small (diagonals over 1e+-8 and 2^+-41 with odd and negative exponents, n =
+    1..12, pivots that are not positive), densely stored (row stride n), checked as check_small does"""
+    name = "spd_scaled12"
+    cs, ref = small_cases("spd_small"), _small_ref("spd_small")
+    bar = inverse_bar(name) if bar is None else bar
+    din = np.full((len(cs), 144), np.nan)
+    for b, (kind, n, A) in enumerate(cs):
+        din[b, :n * n] = A.ravel()
+    o = probe.run(build, name, din, np.array([[n] for _, n, _ in cs]), threads)
+    worst = worst_sym = 0.0
+    for b, (kind, n, A) in enumerate(cs):
+        tag = f"{build} {name} t{threads} case {b} ({kind}, n = {n})"
+        assert np.isnan(o[b, n * n:144]).all(), (tag, "written beyond n x n")
+        ok, r = o[b, 144], ref[b][0]
+        if r is None:
+            assert kind == "bad" and ok == 0, (tag, "ok", ok)
+            continue
+        assert ok == 1, (tag, "ok", ok)
+        Xm, kappa = r
+        X = o[b, :n * n].reshape(n, n)
+        assert np.isfinite(X).all(), tag
+        g, nrm = _gfig(X, Xm, kappa)
+        sym = float(np.abs(X - X.T).max())
+        worst, worst_sym = max(worst, g), max(worst_sym, sym / (U64 * kappa * nrm))
+        assert g <= bar, (tag, "g", g, bar)
+        assert sym <= 2.0 * bar * U64 * kappa * nrm, (tag, "|X - X^T|", sym)
+    return dict(worst_g=worst, worst_sym=worst_sym, n=len(cs))
+
+
+def check_gc_inverse(build, name, threads=64, bar=None):
+    if name == "pinv_cod12":
+        return check_pinv_cod(build, PINV_TS, threads, bar)
+    if name in GJ_INSTS:
+        return check_gj_rows(build, name, threads, bar)
+    if name in SPD_REG_INSTS:
+        return check_spd_reg(build, name, threads, bar)
+    return check_spd_scaled(build, threads, bar)
+
+
+@functools.lru_cache(maxsize=None)
+def mmg_cases(name):
+    """(kind, m, kk, n, A, B) with A, B in the shapes OP reads: run-time sizes (1, 1, 1), the full bounds, n at 15, 16, 17 and 33 (the
+    borders of the 16-wide column tiles) where MAXN allows, kk that is no multiple of 4 (the depth of an MFMA step), odd m"""
+    MAXM, MAXN, MAXK, OP = MMG_INSTS[name]
+    rng = np.random.default_rng(6200 + 1000 * MAXM + 31 * MAXN + MAXK + OP)
+    sizes = [(1, 1, 1), (MAXM, MAXK, MAXN), (MAXM, MAXK - 1, MAXN), (MAXM - 1, 5, MAXN - 1), (3, 7, 2), (MAXM, 1, MAXN), (1, MAXK, 1)]
+    sizes += [(MAXM - (i % 2), MAXK - 2 * i, n) for i, n in enumerate((15, 16, 17, 33)) if n <= MAXN]
+    cs = []
+    for c, (m, kk, n) in enumerate(sizes):
+        sa, sb = ((kk, m) if OP == 2 else (m, kk)), ((n, kk) if OP == 1 else (kk, n))
+        for kind in ("ints", "reals") if c < 5 else ("reals",):
+            if kind == "ints":
+                A, B = rng.integers(-9, 10, sa).astype(float), rng.integers(-9, 10, sb).astype(float)
+            else:
+                A, B = rng.standard_normal(sa) * 2.0 ** rng.integers(-20, 21, sa), rng.standard_normal(sb) * 2.0 ** rng.integers(-20, 21, sb)
+            cs.append((kind, m, kk, n, A, B))
+    return cs
+
+
+@functools.lru_cache(maxsize=None)
+def _mmg_ref(name):
+    """per case the exact product and the exact |A||B| (as _gemm_ref), floats of the 50-digit sums"""
+    OP = MMG_INSTS[name][3]
+    out = []
+    for kind, m, kk, n, A, B in mmg_cases(name):
+        if kind == "ints":  # (exact in int64; no bar to scale)
+            D = (A.T if OP == 2 else A).astype(np.int64) @ (B.T if OP == 1 else B).astype(np.int64)
+            out.append(([[mpf(int(v)) for v in r] for r in D], None))
+            continue
+        Am, Bm = _mpm(A.T if OP == 2 else A), _mpm(B.T if OP == 1 else B)
+        Bc = [[Bm[k][j] for k in range(kk)] for j in range(n)]
+        D = [[mp.fdot(Am[i], Bc[j]) for j in range(n)] for i in range(m)]
+        Ab = [[mp.fsum(abs(x * y) for x, y in zip(Am[i], Bc[j])) for j in range(n)] for i in range(m)]
+        out.append((D, Ab))
+    return out
+
+
+def check_mmg(build, name, threads=64):
+    """mmg at run-time sizes inside its compile-time bounds.  Bar: gamma_{kk+1} (|A||B|), as check_gemm derives it; integers exactly;
+    nothing stored outside m x n (the operands are NaN outside the run-time sizes: an unmasked read shows in the result)"""
+    MAXM, MAXN, MAXK, OP = MMG_INSTS[name]
+    cs, ref = mmg_cases(name), _mmg_ref(name)
+    SA, SB = MAXM * MAXK, MAXK * MAXN
+    din = np.full((len(cs), SA + SB), np.nan)
+    for b, (kind, m, kk, n, A, B) in enumerate(cs):
+        din[b, :A.size] = A.ravel()
+        din[b, SA:SA + B.size] = B.ravel()
+    o = probe.run(build, name, din, np.array([[m, kk, n] for _, m, kk, n, _, _ in cs]), threads)
+    worst = 0.0
+    for b, (kind, m, kk, n, A, B) in enumerate(cs):
+        tag = f"{build} {name} t{threads} case {b} ({kind}, m kk n = {m} {kk} {n})"
+        assert (o[b, m * n:] == probe.FRAME_SENTINEL).all(), (tag, "stored outside m x n")
+        D = o[b, :m * n].reshape(m, n)
+        assert np.isfinite(D).all(), tag
+        Dr, Ab = ref[b]
+        g = gamma(kk + 1)
+        for i in range(m):
+            for j in range(n):
+                e = float(abs(mpf(float(D[i, j])) - Dr[i][j]))
+                bar = 0.0 if kind == "ints" else g * float(Ab[i][j])
+                assert e <= bar, (tag, i, j, D[i, j], float(Dr[i][j]), e, bar)
+                if kind == "reals" and Ab[i][j] > 0:
+                    worst = max(worst, e / (U64 * float(Ab[i][j])))
+    return dict(worst_u=worst, n=len(cs))
+
+
+def check_gc_refusals(build):
+    import pytest
+
+    for name, ip in (("pinv_cod12", [0]), ("pinv_cod12", [13]), ("gj_rows6", [7, 0]), ("gj_rows12", [0, 1]), ("gj_rows18", [19, 0]),
+                     ("gj_rows18", [4, 2]), ("spd_scaled12", [0]), ("spd_scaled12", [13]), ("mmg_12_39_39_nn", [0, 1, 1]),
+                     ("mmg_12_39_39_nn", [13, 39, 39]), ("mmg_12_12_39_nt", [12, 40, 12]), ("mmg_33_12_12_tn", [33, 12, 13]),
+                     ("mmg_12_33_12_nn", [12, 0, 33])):
+        sz = probe.sizes(build, name)
+        with pytest.raises(RuntimeError, match="outside"):
+            probe.run(build, name, np.zeros((1, sz[0])), np.array([ip]))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # bars of the inverses
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -753,15 +1193,18 @@ def inverse_bar(name):
 
 
 def check_inverse(build, name, threads=64, bar=None):
+    if name in GC_INVERSE_INSTS:
+        return check_gc_inverse(build, name, threads, bar)
     return check_sweep(build, name, threads, bar) if name in SWEEP_INSTS else check_small(build, name, threads, bar)
 
 
 def write_tolerances(path=TOL_FILE):
     lines = ["# worst g = |X - X_mp|max / (u kappa_2(A) |X_mp|max) of the HOST build of the wave-routine probe against the 50-digit mpmath inverse,",
              "# per instantiation (python -m tests.wave_cases --write-tolerances; riding right-hand sides included).  tests/wave_cases.py sets the",
-             "# bar of both builds at 10 x this value and never below 10.  sym: |X - X^T|max in the same unit.",
+             "# bar of both builds at 10 x this value and never below 10.  sym: |X - X^T|max in the same unit (0: a general matrix).",
+             "# pinv_cod12: g against the 50-digit restatement of the reference's rank rule, kappa over the kept singular values.",
              "# instantiation worst_g sym cases"]
-    for name in list(SWEEP_INSTS) + list(SMALL_INSTS):
+    for name in list(SWEEP_INSTS) + list(SMALL_INSTS) + list(GC_INVERSE_INSTS):
         r = check_inverse("emu", name, bar=1e300)
         lines.append(f"{name} {r['worst_g']:.3e} {r['worst_sym']:.3e} {r['n']}")
         print(lines[-1], flush=True)
@@ -793,9 +1236,12 @@ def write_device_figures(path=DEV_FILE):
     for name in AXPY_INSTS:
         r = both(lambda t: check_rows_axpy("gpu", name, t))
         lines.append(f"{name}: worst error {max(x['worst_u'] for x in r):.3f} u (|acc| + sum|a||x|) (bar ~ {AXPY_INSTS[name][0] + 1})")
-    for name in list(SWEEP_INSTS) + list(SMALL_INSTS):
+    for name in list(SWEEP_INSTS) + list(SMALL_INSTS) + list(GC_INVERSE_INSTS):
         r = both(lambda t: check_inverse("gpu", name, t))
         lines.append(f"{name}: worst g {max(x['worst_g'] for x in r):.3e}, sym {max(x['worst_sym'] for x in r):.3e} (bar {inverse_bar(name):.3g})")
+    for name in MMG_INSTS:
+        r = both(lambda t: check_mmg("gpu", name, t))
+        lines.append(f"{name}: worst error {max(x['worst_u'] for x in r):.3f} u |A||B| (bar gamma_(kk+1) <= ~ {MMG_INSTS[name][2] + 1})")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))

@@ -1,6 +1,6 @@
 """ctypes loader of the wave-routine probe (wave_probe_body.h).  TEST HARNESS ONLY.
 
-The probe runs the shipped text of the device-only wave routines (dwbc_wave.h, dwbc_cycle2.h, dwbc_cycle2p.h) alone, in two builds of
+The probe runs the shipped text of the device-only wave routines (dwbc_wave.h, dwbc_cycle2.h, dwbc_cycle2p.h, dwbc_cycle_gc.h) alone, in two builds of
 the same source: ``"emu"`` (host emulation, built here on demand like tests/emu) and ``"gpu"`` (libdwbc_wave_probe.so, made by
 ``__graft_entry__.build()``; one wavefront per problem, 64 or 128 threads per block).  Nothing touches the GPU at import.
 

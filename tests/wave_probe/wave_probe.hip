@@ -1,8 +1,8 @@
 // wave_probe.hip -- TEST HARNESS ONLY: the C entries of the wave-routine probe (wave_probe_body.h) and its fp64 instantiations.
 //   hipcc --offload-arch=gfx950            -> libdwbc_wave_probe.so      (device: allocates, copies, launches, synchronises, copies back)
 //   g++ -x c++ -DDWBC_HOST_EMU             -> libdwbc_wave_probe_emu.so  (host emulation of the same text)
-// The 39- and 33-wide sweeps are instantiated in wave_probe_sweeps.hip (they are most of the compile time), the fp32 forms in
-// wave_probe_f32.hip.  The instantiation table below is what tests/wave_probe/probe.py looks its names up in.
+// The 39- and 33-wide sweeps are instantiated in wave_probe_sweeps.hip (they are most of the compile time), the routines of the
+// general-contact kernel in wave_probe_gc.hip, the fp32 forms in wave_probe_f32.hip.  The instantiation table below is what tests/wave_probe/probe.py looks its names up in.
 #ifndef DWBC_HOST_EMU
 #include <hip/hip_runtime.h>
 #endif
@@ -16,6 +16,7 @@ using namespace dwbc;
 
 extern "C" const char *wave_probe_run_f32(int which, const void *args, int threads);     // wave_probe_f32.hip: 0 lanes, 1 math
 extern "C" const char *wave_probe_run_sweep(int kind, const void *args, int threads);    // wave_probe_sweeps.hip
+extern "C" const char *wave_probe_run_gc(int kind, const void *args, int threads);       // wave_probe_gc.hip
 
 namespace {
 
@@ -31,12 +32,15 @@ template <int W>
 const char *run_f32(const WpArgs &a, int threads) { return wave_probe_run_f32(W, &a, threads); }
 template <int K>
 const char *run_sweep(const WpArgs &a, int threads) { return wave_probe_run_sweep(K, &a, threads); }
+template <int K>
+const char *run_gc(const WpArgs &a, int threads) { return wave_probe_run_gc(K, &a, threads); }
 const char *no_check(const int *) { return nullptr; }
 
 #define WP_INST(name, fam, ...) Inst{name, fam, __VA_ARGS__::NIN, __VA_ARGS__::NIP, __VA_ARGS__::NOUT, &__VA_ARGS__::check, &wp_run<__VA_ARGS__>}
 #define WP_GEMM(MR, NCV, KV) \
     WP_INST("gemm_" #MR "_" #NCV "_" #KV, kGemm, WpGemm<MR, NCV, KV, false, false>), WP_INST("gemm_" #MR "_" #NCV "_" #KV "_fc", kGemm, WpGemm<MR, NCV, KV, true, false>)
 #define WP_SWEEP(name, K) Inst{name, kInverse, WpSweep<K>::NIN, WpSweep<K>::NIP, WpSweep<K>::NOUT, &no_check, &run_sweep<K>}
+#define WP_GC(name, fam, K, ...) Inst{name, fam, __VA_ARGS__::NIN, __VA_ARGS__::NIP, __VA_ARGS__::NOUT, &__VA_ARGS__::check, &run_gc<K>}
 const Inst kInst[] = {
     WP_INST("lanes", kLanes, WpLanes),
     Inst{"lanes_f32", kLanes, WpLanes::NIN, WpLanes::NIP, WpLanes::NOUT, &WpLanes::check, &run_f32<0>},
@@ -59,6 +63,13 @@ const Inst kInst[] = {
     WP_SWEEP("sweep_lds33", 4),
     WP_INST("spd_small", kInverse, WpSmall<0>), WP_INST("spd12_lds", kInverse, WpSmall<1>), WP_INST("spd12_lds_inplace", kInverse, WpSmall<2>),
     WP_INST("chol6", kInverse, WpSmall<3>), WP_INST("chol6_x3", kInverse, WpChol3),
+    // the general-contact kernel's routines (K: the case of wave_probe_run_gc), mmg at the bounds of the TG = 12 build
+    WP_GC("pinv_cod12", kInverse, 0, WpPinvCod),
+    WP_GC("gj_rows6", kInverse, 1, WpGjRows<6>), WP_GC("gj_rows12", kInverse, 2, WpGjRows<12>), WP_GC("gj_rows18", kInverse, 3, WpGjRows<18>),
+    WP_GC("spd_reg39_lds", kInverse, 4, WpSpdReg<39, true>), WP_GC("spd_reg33_lds", kInverse, 5, WpSpdReg<33, true>),
+    WP_GC("spd_reg33_rl", kInverse, 6, WpSpdReg<33, false>), WP_GC("spd_scaled12", kInverse, 7, WpSpdScaled),
+    WP_GC("mmg_12_39_39_nn", kGemm, 8, WpMmg<12, 39, 39, 0>), WP_GC("mmg_12_12_39_nt", kGemm, 9, WpMmg<12, 12, 39, 1>),
+    WP_GC("mmg_33_12_12_tn", kGemm, 10, WpMmg<33, 12, 12, 2>), WP_GC("mmg_12_33_12_nn", kGemm, 11, WpMmg<12, 33, 12, 0>),
 };
 constexpr int kNInst = (int)(sizeof(kInst) / sizeof(kInst[0]));
 constexpr int kMaxB = 512;

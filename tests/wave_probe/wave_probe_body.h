@@ -1,5 +1,5 @@
 // wave_probe_body.h -- TEST HARNESS ONLY.  Runs the shipped text of the device-only wave routines (libdwbc_amd/csrc/dwbc_wave.h,
-// dwbc_cycle2.h, dwbc_cycle2p.h) alone, on operands of the caller's choosing: one set of templates, compiled for the device
+// dwbc_cycle2.h, dwbc_cycle2p.h, dwbc_cycle_gc.h) alone, on operands of the caller's choosing: one set of templates, compiled for the device
 // (wave_probe.hip -> libdwbc_wave_probe.so, one wavefront per problem, 64 or 128 threads per block -- the two-wave kernel runs these
 // routines in wave 1, where lane = threadIdx.x & 63) and for the host (the same files with DWBC_HOST_EMU -> libdwbc_wave_probe_emu.so).
 // The probe includes the shipped headers and calls the shipped functions; it holds no copy of any of them, and nothing of it is
@@ -364,6 +364,174 @@ struct WpChol3 {
             for (int e = lane; e < 72; e += 64) out[e] = (double)L[108 + e];
             for (int e = lane; e < 36; e += 64) out[72 + e] = (double)L[72 + e];
             if (lane == 0) out[108] = ok3[0], out[109] = ok3[1], out[110] = ok3[2];
+        }
+    }
+};
+// ---- 6. the routines of the general-contact kernel (dwbc_cycle_gc.h) and the rank-revealing pseudo-inverse it shares with the
+// product kernels (dwbc_cycle2.h).  fp64 only: that kernel refuses fp32.  Instantiated in wave_probe_gc.hip.
+// The thread-strided routines take Thr{lane} with NT = 64 on the device and Thr{0} with NT = 1 on the host, as the kernels do.
+#ifdef DWBC_HOST_EMU
+constexpr int kWpNT = 1;
+#define WP_THR Thr{0}
+inline int wp_uni(int v) { return v; }
+#else
+constexpr int kWpNT = 64;
+#define WP_THR Thr{lane}
+__device__ __forceinline__ int wp_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }  // (run-time sizes are wave-uniform in the kernels)
+#endif
+
+// pinv_cod_small with the scratch its callers give it: three 12 x 12 blocks and 3 x 12 reals.  ip: t = 1..12.  in: 144, the block
+// densely (row stride t) in the leading t t words.  out: Out (144: t x t densely, the rest keeps the frame sentinel -- all of it on a
+// full-rank verdict), the returned rank, and the 36 words behind vec (must stay NaN)
+struct WpPinvCod {
+    static constexpr int oM = 0, oO = 144, oQ = 288, oG = 432, oT = 576, oV = 720, oGd = 756, LDS = 792;
+    static constexpr int NIN = 144, NIP = 1, NOUT = 144 + 1 + 36;
+    static const char *check(const int *ip) { return (ip[0] < 1 || ip[0] > 12) ? "t outside 1..12" : nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int t = wp_uni(ip[0]);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= oO && e < oO + 144) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 144; e += 64) L[oM + e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        int rank = -1;
+        rank = pinv_cod_small<kWpNT, 12>(WP_THR, L + oM, t, kCodThreshold, L + oO, L + oQ, L + oG, L + oT, L + oV);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 144; e += 64) out[e] = (double)L[oO + e];
+            for (int e = lane; e < 36; e += 64) out[145 + e] = (double)L[oGd + e];
+            if (lane == 0) out[144] = rank;
+        }
+    }
+};
+
+// gj_inverse_rows<NMAX>.  ip: n = 1..NMAX, in place (0 / 1).  in: NMAX^2, the matrix densely (row stride n) in the leading n n
+// words.  out: the output block (NMAX^2: out of place the frame sentinel behind n n words, in place what the input held), pivot ratio
+template <int NMAX>
+struct WpGjRows {
+    static constexpr int SZ = NMAX * NMAX, oA = 0, oO = wp_ev(SZ), oW = 2 * wp_ev(SZ), LDS = oW + 2 * NMAX + 2;
+    static constexpr int NIN = SZ, NIP = 2, NOUT = SZ + 1;
+    static const char *check(const int *ip) {
+        if (ip[0] < 1 || ip[0] > NMAX) return "n outside 1..NMAX";
+        if (ip[1] < 0 || ip[1] > 1) return "in-place flag outside 0..1";
+        return nullptr;
+    }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int n = wp_uni(ip[0]);
+        real_t *Ai = wp_uni(ip[1]) ? L + oA : L + oO;
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= oO && e < oO + SZ) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < SZ; e += 64) L[oA + e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        const real_t ratio = gj_inverse_rows<NMAX, kWpNT>(WP_THR, L + oA, n, n, Ai, n, L + oW);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < SZ; e += 64) out[e] = (double)Ai[e];
+            if (lane == 0) out[SZ] = (double)ratio;
+        }
+    }
+};
+
+// spd_inverse_reg<NN> in place, as the kernel calls it.  LDSFEED: the pivot column through colbuf (sweep_inverse_lds), else the
+// v_readlane feed (sweep_inverse_rl).  in: NN x NN.  out: NN x NN, ok
+template <int NN, bool LDSFEED>
+struct WpSpdReg {
+    static constexpr int oC = wp_ev(NN * NN), LDS = oC + 64 + 2;
+    static constexpr int NIN = NN * NN, NIP = 1, NOUT = NN * NN + 1;
+    static const char *check(const int *) { return nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < NN * NN; e += 64) L[e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        const int ok = spd_inverse_reg<NN>(L, NN, L, NN, LDSFEED ? L + oC : nullptr);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < NN * NN; e += 64) out[e] = (double)L[e];
+            if (lane == 0) out[NN * NN] = ok;
+        }
+    }
+};
+
+// spd_inverse_scaled<12> in place.  ip: n = 1..12.  in: 144, the matrix densely (row stride n) in the leading n n words.  out: 144, ok
+struct WpSpdScaled {
+    static constexpr int oC = 144, LDS = 144 + 12 + 2;
+    static constexpr int NIN = 144, NIP = 1, NOUT = 145;
+    static const char *check(const int *ip) { return (ip[0] < 1 || ip[0] > 12) ? "n outside 1..12" : nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int n = wp_uni(ip[0]);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 144; e += 64) L[e] = (real_t)in[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        const int ok = spd_inverse_scaled<12>(L, n, n, L, n, L + oC);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < 144; e += 64) out[e] = (double)L[e];
+            if (lane == 0) out[144] = ok;
+        }
+    }
+};
+
+// mmg<MAXM, MAXN, MAXK, OP>.  ip: m, kk, n (1 .. the bounds).  in: A then B, each densely in the leading words of its MAXM MAXK /
+// MAXK MAXN block (OP 0: A m x kk, B kk x n;  1: A m x kk, B n x kk;  2: A kk x m, B kk x n), NaN behind.  out: the C block
+// (MAXM MAXN: m x n densely, the frame sentinel behind)
+template <int MAXM, int MAXN, int MAXK, int OP>
+struct WpMmg {
+    static constexpr int SA = MAXM * MAXK, SB = MAXK * MAXN, SC = MAXM * MAXN;
+    static constexpr int oA = 0, oB = wp_ev(SA), oC = oB + wp_ev(SB), LDS = oC + wp_ev(SC);
+    static constexpr int NIN = SA + SB, NIP = 3, NOUT = SC;
+    static const char *check(const int *ip) {
+        if (ip[0] < 1 || ip[0] > MAXM) return "m outside 1..MAXM";
+        if (ip[1] < 1 || ip[1] > MAXK) return "kk outside 1..MAXK";
+        if (ip[2] < 1 || ip[2] > MAXN) return "n outside 1..MAXN";
+        return nullptr;
+    }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int m = wp_uni(ip[0]), kk = wp_uni(ip[1]), n = wp_uni(ip[2]);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= oC && e < oC + SC) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < SA; e += 64) L[oA + e] = (real_t)in[e];
+            for (int e = lane; e < SB; e += 64) L[oB + e] = (real_t)in[SA + e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        mmg<MAXM, MAXN, MAXK, OP>(L + oC, n, L + oA, OP == 2 ? m : kk, L + oB, OP == 1 ? kk : n, m, kk, n);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < SC; e += 64) out[e] = (double)L[oC + e];
         }
     }
 };
