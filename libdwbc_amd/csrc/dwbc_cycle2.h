@@ -1137,6 +1137,12 @@ DWBC_DEV void internal_wrench_basis(Thr th, const real_t *Pc, const real_t *JCt,
 // fp64 device build: one 16 x 16 accumulator tile per 16 columns, v_mfma_f64_16x16x4_f64 over K = 33 (9 steps); the A operand is the
 // ROTATED row of Jbar, formed on the fly from three LDS reads (operand layout verified on gfx950 by tools/ubench/mfma_stage.hip:
 // A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D[i = (l >> 4) + 4 r][j = l & 15]).  BASELINE configs[1] has exactly 16 columns.
+// One active contact (cd = 6): the device body still stores all 12 rows, rows 6..11 from R_1 (S::Rc + 9, which stage 1 does not write
+// for an inactive contact: stale LDS) and rows 6..11 of Jbar^T (zero); the host body stores cd rows.  Nothing reads those rows into a
+// QP row, a status or an output: the cone lanes of qp_rows_and_solve / redis_row_norms (and of the two-wave cycle's row fill) exist for
+// rr < ncone = 10 nc only, so row2 / rowo < cd; every other lane reads row 0 and masks it with a select; fv[r] and wacc[r], r >= cd, are
+// formed from row r and read back only into fv[r] / wacc[r] of the same r; the wrench epilogues select 0 for i >= cd.
+// tests/wave_cases.py check_wrench_maps runs that case with NaN in R_1 and in rows 6..11 of Jbar^T: rows 0..5 stay finite and exact.
 template <int N, int NT, class S>
 DWBC_DEV void wrench_maps(Thr th, const Setup &su, real_t *L, const real_t *JbT, int cd, int k, real_t *WM) {
     constexpr int M = N - 6, T = S::T, WLD = S::WLD;
@@ -1198,6 +1204,49 @@ DWBC_DEV void wrench_maps(Thr th, const Setup &su, real_t *L, const real_t *JbT,
         WM[i * WLD + col] = acc;
     }
     DWBC_SYNC();
+}
+
+// J A^-1 J^T = Y J_C^T of stage 1 (dwbc_cycle2_stage1.inc, dwbc_redistribute.h): Yt and JCt are the TRANSPOSED N x C blocks (row
+// stride C) whose rows beyond cd are zero; the result is the C x C block of row stride C at L + OUT, zero outside cd x cd (the device
+// body computes all of it, the host loops only cd x cd).  No barrier on either side: the callers hold them.  (The block is named by
+// the LDS base and a compile-time offset, not by a pointer: the index expression of the stores is then the one the inline text had.)
+// fp64 device build: one 16 x 16 accumulator tile.  Both operands are the transposed blocks, so A[i][k] and B[k][j] are the same
+// address pattern (row k of the block, entry i resp. j); K = N in steps of 4.  Rows / columns 12..15 of the tile are padding
+// (whatever they read stays in their own row / column of the result); rows and columns beyond cd are zero because Y and J_C are.
+// (Operand layout: see wrench_maps.)
+template <int N, int C, int NT, int OUT>
+DWBC_DEV void contact_gram(Thr th, const real_t *Yt, const real_t *JCt, int cd, real_t *L) {
+    DWBC_LANE_DECL;
+#if !defined(DWBC_HOST_EMU)
+    if constexpr (sizeof(real_t) == 8) {
+        static_assert(C == 12, "rows lk + 4 r, r < 3, of one tile");
+        typedef double lc_d4 __attribute__((ext_vector_type(4)));
+        const int li = lane & 15, lk = lane >> 4;
+        lc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s_ = 0; s_ < (N + 3) / 4; s_++) {
+            const int c = 4 * s_ + lk;
+            const bool in = c < N;
+            const int cc = in ? c : N - 1;
+            real_t av = Yt[cc * C + (li < C ? li : 0)], bv = JCt[cc * C + (li < C ? li : 0)];
+            av = in ? av : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        }
+        if (li < C) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) L[OUT + (lk + 4 * r) * C + li] = acc[r];
+        }
+    } else
+#endif
+    for (int idx = th.tid; idx < C * C; idx += NT) {
+        const int i = idx / C, j = idx - i * C;
+        real_t a4[4] = {real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0)};
+        if (i < cd && j < cd) {
+#pragma unroll
+            for (int c = 0; c < N; c++) a4[c & 3] += Yt[c * C + i] * JCt[c * C + j];
+        }
+        L[OUT + idx] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+    }
 }
 
 // EXTRAS = false compiles the optional paths out (task-link trajectories, qdot outputs, COM / TASK_CUSTOM levels, hqp = false):

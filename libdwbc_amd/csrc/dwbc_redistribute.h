@@ -255,36 +255,8 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
         }
     }
     DWBC_SYNC();
-    // J A^-1 J^T = Y J_C^T in a C x C block, zero outside cd x cd (operand layout of the tile: see stage 1 of the cycle)
-#if !defined(DWBC_HOST_EMU)
-    if constexpr (sizeof(real_t) == 8) {
-        typedef double lc_d4 __attribute__((ext_vector_type(4)));
-        const int li = lane & 15, lk = lane >> 4;
-        lc_d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s_ = 0; s_ < (N + 3) / 4; s_++) {
-            const int c = 4 * s_ + lk;
-            const bool in = c < N;
-            const int cc = in ? c : N - 1;
-            real_t av = Yt[cc * C + (li < C ? li : 0)], bv = JCt[cc * C + (li < C ? li : 0)];
-            av = in ? av : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-        }
-        if (li < C) {
-#pragma unroll
-            for (int r = 0; r < 3; r++) L[S::c_s2 + (lk + 4 * r) * C + li] = acc[r];
-        }
-    } else
-#endif
-    for (int idx = th.tid; idx < C * C; idx += NT) {
-        const int i = idx / C, j = idx - i * C;
-        real_t a4[4] = {real_t(0.0), real_t(0.0), real_t(0.0), real_t(0.0)};
-        if (i < cd && j < cd) {
-#pragma unroll
-            for (int c = 0; c < N; c++) a4[c & 3] += Yt[c * C + i] * JCt[c * C + j];
-        }
-        L[S::c_s2 + idx] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-    }
+    // J A^-1 J^T = Y J_C^T in a C x C block, zero outside cd x cd (contact_gram, dwbc_cycle2.h: the tile stage 1 of the cycle takes)
+    contact_gram<N, C, NT, S::c_s2>(th, Yt, JCt, cd, L);
     if (cd > 0) {
         if (!spd_inverse_small(L + S::c_s2, C, cd, Lam, C, L + S::c_s1)) st_contact = 0;  // Lambda_c (wbd.cpp:115)
     }

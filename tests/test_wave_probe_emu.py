@@ -15,7 +15,7 @@ BUILD = "emu"
 def test_instantiation_table_holds_every_family():
     t = probe.table(BUILD)
     names = ["lanes", "lanes_f32", "math", "math_f32"] + [g[0] for g in wc.GEMM_INSTS] + list(wc.DOT_INSTS) + list(wc.AXPY_INSTS)
-    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS)
+    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS) + list(wc.TILE_INSTS)
     assert sorted(t) == sorted(names)
 
 
@@ -90,6 +90,24 @@ def test_spd_inverse_scaled():
 @pytest.mark.parametrize("name", list(wc.MMG_INSTS))
 def test_mmg(name):
     wc.check_mmg(BUILD, name)
+
+
+@pytest.mark.parametrize("name", list(wc.GRAM_INSTS))
+def test_contact_gram(name):
+    """contact_gram (dwbc_cycle2.h: J A^-1 J^T = Y J_C^T of stage 1, of the redistribution and of the gravity compensation) alone: K
+    padding with 0 to 3 masked lane groups, cd = 6 and 12, the unit sweep over every (i, j) and one reduction index per K step"""
+    wc.check_gram(BUILD, name)
+
+
+@pytest.mark.parametrize("name", list(wc.WRENCH_INSTS))
+def test_wrench_maps(name):
+    """wrench_maps (dwbc_cycle2.h) alone over every hierarchy of wave_cases.WRENCH_HIER: col_src against a restatement written from the
+    comment above the function, K padding, partial tiles, one contact with NaN in the stale operands"""
+    wc.check_wrench(BUILD, name)
+
+
+def test_wrench_maps_layout():
+    wc.check_wrench_layout(BUILD)
 
 
 def test_committed_tolerances_are_the_host_figures(tmp_path):

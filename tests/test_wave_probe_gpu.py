@@ -1,7 +1,8 @@
 """-m gpu: the wave-routine probe (tests/wave_probe) in its DEVICE build -- the bodies that ship behind the DWBC_HOST_EMU forks (DPP
 reductions and scans, v_readlane broadcasts, fast_rcp / fast_rsqrt / sincos_r, wave_gemm on the matrix cores, the LDS-fed sweeps,
 spd_inverse12_lds, the three-group Cholesky inverse, the hand-batched row products, and the general-contact kernel's pinv_cod_small,
-gj_inverse_rows, spd_inverse_reg, spd_inverse_scaled and mmg), each alone on the cases and against the 50-digit
+gj_inverse_rows, spd_inverse_reg, spd_inverse_scaled and mmg, and the two in-place matrix-core tiles of the cycle, contact_gram and
+wrench_maps), each alone on the cases and against the 50-digit
 references of tests/wave_cases.py, with 64 and with 128 threads per block (the two-wave kernel runs them in wave 1).  One launch per
 instantiation.  The host twin, which validates the same cases and references, is tests/test_wave_probe_emu.py."""
 import pytest
@@ -16,7 +17,7 @@ THREADS = pytest.mark.parametrize("threads", [64, 128])
 
 def test_instantiation_table_holds_every_family():
     names = ["lanes", "lanes_f32", "math", "math_f32"] + [g[0] for g in wc.GEMM_INSTS] + list(wc.DOT_INSTS) + list(wc.AXPY_INSTS)
-    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS)
+    names += list(wc.SWEEP_INSTS) + list(wc.SMALL_INSTS) + list(wc.GC_INVERSE_INSTS) + list(wc.MMG_INSTS) + list(wc.TILE_INSTS)
     assert sorted(probe.table(BUILD)) == sorted(names)
 
 
@@ -107,3 +108,24 @@ def test_spd_inverse_scaled(threads):
 @pytest.mark.parametrize("name", list(wc.MMG_INSTS))
 def test_mmg(name, threads):
     wc.check_mmg(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.GRAM_INSTS))
+def test_contact_gram(name, threads):
+    """contact_gram (dwbc_cycle2.h: J A^-1 J^T = Y J_C^T of stage 1, of the redistribution and of the gravity compensation) alone: K
+    padding with 0 to 3 masked lane groups, cd = 6 and 12, the unit sweep over every (i, j) and one reduction index per K step"""
+    wc.check_gram(BUILD, name, threads)
+
+
+@THREADS
+@pytest.mark.parametrize("name", list(wc.WRENCH_INSTS))
+def test_wrench_maps(name, threads):
+    """wrench_maps (dwbc_cycle2.h) alone over every hierarchy of wave_cases.WRENCH_HIER: col_src against a restatement written from the
+    comment above the function, K padding, partial tiles, one contact with NaN in the stale operands"""
+    wc.check_wrench(BUILD, name, threads)
+
+
+@THREADS
+def test_wrench_maps_layout(threads):
+    wc.check_wrench_layout(BUILD, threads)

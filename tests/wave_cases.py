@@ -1,7 +1,8 @@
 """Cases, 50-digit mpmath references and checks of the wave-routine probe (tests/wave_probe): the device-only bodies behind the
 DWBC_HOST_EMU forks -- cross-lane primitives, scalar math, wave_gemm, the inverses and the batched row products -- and the routines
 of the general-contact kernel (section 6: the rank-revealing pseudo-inverse, the pivoted Gauss-Jordan inverse, the register-sweep
-inverses, the run-time sized matrix-core product), each alone.
+inverses, the run-time sized matrix-core product) and the two in-place matrix-core tiles of the cycle (section 7: contact_gram and
+wrench_maps), each alone.
 
 Both builds of the probe run the same cases against the same references: tests/test_wave_probe_emu.py (host emulation: validates the
 cases and the references, and is where the bars of the inverses come from) and tests/test_wave_probe_gpu.py (the device bodies).
@@ -1162,13 +1163,367 @@ def check_mmg(build, name, threads=64):
     return dict(worst_u=worst, n=len(cs))
 
 
+# ====================================================================================================================================
+# 7. the two in-place matrix-core tiles of the cycle: contact_gram and wrench_maps (dwbc_cycle2.h)
+# ====================================================================================================================================
+# Both families return the wave's whole LDS slice (wave_probe_body.h, section 7), so every check sees the guards, the operands as they
+# read back and the output block.  Bars: integers exactly; reals gamma_{K+3} sum_c (|R||J|)_c |rhs_c| -- the bound of check_gemm with
+# three more roundings for the three-term row of A_rot (contact_gram has no such row: its bound is the looser for it), K = N for the
+# Gram tile and K = M for the wrench maps, in ANY order of summation; the sum is taken in mpmath.
+GRAM_INSTS = {"gram_39": 39, "gram_37": 37, "gram_23": 23, "gram_24": 24, "gram_50": 50}
+WRENCH_INSTS = {"wrench_39": 39, "wrench_37": 37, "wrench_23": 23, "wrench_24": 24, "wrench_50": 50}
+TILE_INSTS = tuple(GRAM_INSTS) + tuple(WRENCH_INSTS)
+# (cd, k, t_dof): 1 + sum t + k columns -- one full tile (BASELINE's shape), one partial tile, a partial second tile ([6, 6, 3]: the
+# third level's block, columns 13..15, ends at the tile boundary), a block across the boundary ([3, 6, 6]: the null block, columns
+# 16..21, starts the second tile; [6, 3, 6]: the third level's block is columns 10..15, offsets 0, 6, 9), the maximum of 31 (its third
+# level's block, columns 13..18, straddles column 16, the tile boundary), two single-contact shapes without a null block
+WRENCH_HIER = [(12, 6, (6, 3)), (12, 6, (3,)), (12, 6, (6, 6, 3)), (12, 6, (3, 6, 6)), (12, 6, (6, 3, 6)), (12, 6, (6, 6, 6, 6)),
+               (6, 0, (6, 3)), (6, 0, (3,))]
+WRENCH_LAYOUT_HIER = [(12, 6, (6, 6, 6, 6)), (6, 0, (6, 3))]
+
+
+def _bits_equal(a, b):
+    return np.array_equal(np.ascontiguousarray(a, np.float64).view(np.uint64), np.ascontiguousarray(b, np.float64).view(np.uint64))
+
+
+def _spread(rng, shape):
+    return rng.standard_normal(shape) * 2.0 ** rng.integers(-20, 21, shape)
+
+
+# ---- contact_gram
+def _gram_offsets(N):
+    oY = 2
+    oJ = oY + 12 * N + 2
+    oO = oJ + 12 * N + 2
+    return oY, oJ, oO, oO + 144 + 2
+
+
+@functools.lru_cache(maxsize=None)
+def gram_cases(N):
+    """(kind, cd, Yt, JCt), both N x 12 with the columns >= cd zero (the contract of contact_gram): small integers, reals with an exponent
+    spread and one cancelling row, 1e300 in the last reduction row of either or both operands (what the masked duplicate of that row
+    computes must not be added), each at cd = 12 and at cd = 6 (one contact)"""
+    rng = np.random.default_rng(7100 + N)
+    cs = []
+
+    def cut(A, cd):
+        A[:, cd:] = 0.0
+        return A
+
+    for c in range(4):
+        cd = 12 if c < 2 else 6
+        cs.append(("ints", cd, cut(rng.integers(-9, 10, (N, 12)).astype(float), cd), cut(rng.integers(-9, 10, (N, 12)).astype(float), cd)))
+    for c in range(6):
+        cd = 12 if c < 4 else 6
+        Y, J = _spread(rng, (N, 12)), _spread(rng, (N, 12))
+        Y[1:, 0] = Y[0, 0]  # row 0 of Y J^T: equal factors against a column sum that cancels
+        J[1:, :] = -J[:1, :] / (N - 1)
+        cs.append(("reals", cd, cut(Y, cd), cut(J, cd)))
+    for c, (hy, hj) in enumerate(((True, True), (True, False), (False, True), (True, False))):
+        cd = 12 if c < 3 else 6
+        Y, J = rng.integers(1, 10, (N, 12)).astype(float), rng.integers(1, 10, (N, 12)).astype(float)
+        if hy:
+            Y[N - 1, :] = 1.0e300
+        if hj:
+            J[N - 1, :] = 1.0e300
+        cs.append(("huge", cd, cut(Y, cd), cut(J, cd)))
+    return cs
+
+
+@functools.lru_cache(maxsize=None)
+def _gram_ref(N):
+    """per case the exact Y J^T and the exact sum_c |Y_ci J_cj| over cd x cd (zero outside), nested lists of mpf"""
+    out = []
+    for kind, cd, Y, J in gram_cases(N):
+        Yc, Jc = [mpv(Y[:, i]) for i in range(cd)], [mpv(J[:, j]) for j in range(cd)]
+        D = [[mp.fdot(Yc[i], Jc[j]) for j in range(cd)] for i in range(cd)]
+        Ab = [[mp.fsum(abs(a * b) for a, b in zip(Yc[i], Jc[j])) for j in range(cd)] for i in range(cd)]
+        out.append((D, Ab))
+    return out
+
+
+def _gram_unpack(o, N, Y, J, tag):
+    """the footprint: guards, operands bit for bit; returns the 12 x 12 block"""
+    oY, oJ, oO, LDS = _gram_offsets(N)
+    assert o.shape == (LDS,), (tag, o.shape)
+    guard = np.r_[0:oY, oJ - 2:oJ, oO - 2:oO, LDS - 2:LDS]
+    assert np.isnan(o[guard]).all(), (tag, "guard words", o[guard])
+    assert _bits_equal(o[oY:oY + 12 * N], Y.ravel()) and _bits_equal(o[oJ:oJ + 12 * N], J.ravel()), (tag, "an operand changed")
+    return o[oO:oO + 144].reshape(12, 12)
+
+
+def _check_block(tag, kind, D, Dr, Ab, rows, cols, g):
+    """D[i, j] against the exact Dr over rows x cols; returns the worst error in units of u Ab"""
+    worst = 0.0
+    for i in range(rows):
+        for j in range(cols):
+            if kind == "ints":
+                assert D[i, j] == float(Dr[i][j]), (tag, i, j, D[i, j], float(Dr[i][j]))
+            elif abs(Dr[i][j]) > mpf(1.7e308):
+                assert D[i, j] == (np.inf if Dr[i][j] > 0 else -np.inf), (tag, i, j, D[i, j])
+            else:
+                assert np.isfinite(D[i, j]), (tag, i, j, D[i, j])
+                e = float(abs(mpf(float(D[i, j])) - Dr[i][j]))
+                bar = g * float(Ab[i][j])
+                assert e <= bar, (tag, i, j, D[i, j], float(Dr[i][j]), e, bar)
+                if kind == "reals" and Ab[i][j] > 0:
+                    worst = max(worst, e / (U64 * float(Ab[i][j])))
+    return worst
+
+
+def _gram_unit_cs(N):
+    """the reduction indices of the unit sweep: the first four, the last two, and one per K step (a different lane group in each)"""
+    return sorted({0, 1, 2, 3, N - 2, N - 1} | {min(4 * s + s % 4, N - 1) for s in range((N + 3) // 4)})
+
+
+def check_gram(build, name, threads=64):
+    """contact_gram<N, 12>: the cases of gram_cases against Y J^T (zero outside cd x cd, exactly), then the exhaustive layout sweep:
+    Yt = e_(c,i), JCt = e_(c,j) gives exactly e_i e_j^T -- a transposed or permuted operand layout, a K step that reads another row,
+    a padding lane that stores, each moves the one"""
+    N = GRAM_INSTS[name]
+    cs, ref = gram_cases(N), _gram_ref(N)
+    din = np.stack([np.concatenate([Y.ravel(), J.ravel()]) for _, _, Y, J in cs])
+    o = probe.run(build, name, din, np.array([[cd] for _, cd, _, _ in cs]), threads)
+    g = gamma(N + 3)
+    worst = 0.0
+    for b, (kind, cd, Y, J) in enumerate(cs):
+        tag = f"{build} {name} t{threads} case {b} ({kind}, cd {cd})"
+        D = _gram_unpack(o[b], N, Y, J, tag)
+        outside = np.ones((12, 12), bool)
+        outside[:cd, :cd] = False
+        assert (D[outside] == 0.0).all(), (tag, "not zero outside cd x cd", D)
+        worst = max(worst, _check_block(tag, kind, D, ref[b][0], ref[b][1], cd, cd, g))
+    units = [(c, i, j) for c in _gram_unit_cs(N) for i in range(12) for j in range(12)]
+    for c0 in range(0, len(units), probe.MAX_B):
+        part = units[c0:c0 + probe.MAX_B]
+        din = np.zeros((len(part), 24 * N))
+        for b, (c, i, j) in enumerate(part):
+            din[b, c * 12 + i] = 1.0
+            din[b, 12 * N + c * 12 + j] = 1.0
+        o = probe.run(build, name, din, np.full((len(part), 1), 12), threads)
+        for b, (c, i, j) in enumerate(part):
+            tag = f"{build} {name} t{threads} unit (c, i, j) = ({c}, {i}, {j})"
+            D = _gram_unpack(o[b], N, din[b, :12 * N], din[b, 12 * N:], tag)
+            E = np.zeros((12, 12))
+            E[i, j] = 1.0
+            assert np.array_equal(D, E), (tag, np.argwhere(D != E))
+    return dict(worst_u=worst, n=len(cs), n_units=len(units))
+
+
+# ---- wrench_maps
+def _wrench_offsets(N):
+    """the probe's LDS map (WpWrenchMap of wave_probe_body.h): offset of Rc, tg, U, NwJw, JbT, WM and the slice length"""
+    M = N - 6
+    Rc = 2
+    tg = Rc + 18 + 2
+    U = tg + ((M + 1) & ~1) + 2
+    Nw = U + 24 * M + 2
+    Jb = Nw + 6 * M + 2
+    wm = Jb + 12 * N + 2
+    return Rc, tg, U, Nw, Jb, wm, wm + 384 + 2
+
+
+def wrench_rhs(M, k, t_dof, tg, U, NwJw):
+    """the right-hand operand [ tg | U_0 | U_1 ... | NwJw ] (M x (1 + sum t_l + k)), restated from the comment above wrench_maps:
+    column 0 is the gravity torque, level l contributes the leading t_l columns of its M x 6 block, the contact-null block its k columns"""
+    return np.hstack([tg.reshape(M, 1)] + [U[l][:, :t] for l, t in enumerate(t_dof)] + [NwJw[:, :k]])
+
+
+def _wrench_record(N, R, JbT, tg, U, NwJw):
+    return np.concatenate([R.ravel(), JbT.ravel(), tg.ravel(), U.ravel(), NwJw.ravel()])
+
+
+def _wrench_ip(cd, k, t_dof):
+    return [cd, k, len(t_dof)] + list(t_dof) + [0] * (4 - len(t_dof))
+
+
+def _wrench_poison(M, cd, k, t_dof, U, NwJw):
+    """NaN in every word of U and NwJw that no column of the hierarchy addresses: a stride, a level or a block taken wrongly reads one"""
+    for l in range(4):
+        U[l][:, (t_dof[l] if l < len(t_dof) else 0):] = np.nan
+    NwJw[:, k:] = np.nan
+
+
+@functools.lru_cache(maxsize=None)
+def wrench_cases(N):
+    """(kind, cd, k, t_dof, R (2, 3, 3), JbT (12, N), tg (M), U (4, M, 6), NwJw (M, 6)) over every hierarchy of WRENCH_HIER: four integer
+    cases, six of reals with an exponent spread (three of them with rows 0..2 cancelling), three with 1e300 in the last reduction row
+    (of J0, of every right-hand block, of both) and, with one contact, two integer and two real cases with NaN in R_1 and in rows 6..11
+    of Jbar^T (kinds "ints1" / "reals1").  R need not be a rotation: the function is bilinear.  The words of U / NwJw beyond the
+    hierarchy's columns hold NaN; columns 0..5 of Jbar^T, which the function never reads, too."""
+    M = N - 6
+    rng = np.random.default_rng(7300 + N)
+    cs = []
+
+    def add(kind, cd, k, t_dof, R, J, tg, U, Nw):
+        _wrench_poison(M, cd, k, t_dof, U, Nw)
+        J[:, :6] = np.nan
+        if kind.endswith("1"):
+            R[1] = np.nan
+            J[6:, :] = np.nan
+        cs.append((kind, cd, k, t_dof, R, J, tg, U, Nw))
+
+    for cd, k, t_dof in WRENCH_HIER:
+        ints = lambda lo, shape: rng.integers(lo, 10, shape).astype(float)
+        for _ in range(4):
+            add("ints", cd, k, t_dof, ints(-9, (2, 3, 3)), ints(-9, (12, N)), ints(-9, M), ints(-9, (4, M, 6)), ints(-9, (M, 6)))
+        for c in range(6):
+            R, J, tg, U, Nw = _spread(rng, (2, 3, 3)), _spread(rng, (12, N)), _spread(rng, M), _spread(rng, (4, M, 6)), _spread(rng, (M, 6))
+            if c < 3:  # rows 0..2 of A_rot Jbar are constant along the reduction, every right-hand column sums to zero
+                J[0:3, 7:] = J[0:3, 6:7]
+                tg[1:] = -tg[0] / (M - 1)
+                U[:, 1:, :] = -U[:, :1, :] / (M - 1)
+                Nw[1:, :] = -Nw[:1, :] / (M - 1)
+            add("reals", cd, k, t_dof, R, J, tg, U, Nw)
+        for hj, hr in ((True, False), (False, True), (True, True)):
+            R, J, tg, U, Nw = ints(1, (2, 3, 3)), ints(1, (12, N)), ints(1, M), ints(1, (4, M, 6)), ints(1, (M, 6))
+            if hj:
+                J[:, N - 1] = 1.0e300
+            if hr:
+                tg[M - 1], U[:, M - 1, :], Nw[M - 1, :] = 1.0e300, 1.0e300, 1.0e300
+            add("huge", cd, k, t_dof, R, J, tg, U, Nw)
+        if cd == 6:
+            for _ in range(2):
+                add("ints1", cd, k, t_dof, ints(-9, (2, 3, 3)), ints(-9, (12, N)), ints(-9, M), ints(-9, (4, M, 6)), ints(-9, (M, 6)))
+                add("reals1", cd, k, t_dof, _spread(rng, (2, 3, 3)), _spread(rng, (12, N)), _spread(rng, M), _spread(rng, (4, M, 6)), _spread(rng, (M, 6)))
+    return cs
+
+
+def _wrench_terms(R, JbT, i, N):
+    """row i of A_rot Jbar[:, 6:] as its three terms: contact a = i / 6, force / moment half h, axis x; the row is column x of R_a
+    (A_rot = blockdiag(R_a^T, R_a^T)) against rows 6 a + 3 h .. + 2 of Jbar^T"""
+    a, h, x = i // 6, (i % 6) // 3, i % 3
+    return [(R[a][y][x], JbT[6 * a + 3 * h + y, 6:]) for y in range(3)]
+
+
+@functools.lru_cache(maxsize=None)
+def _wrench_ref(N):
+    """per case the exact WM[:cd, :ncols] and the exact sum_c (|R||J|)_c |rhs_c| (nested lists of mpf; the integer cases in int64, no bar)"""
+    M = N - 6
+    out = []
+    for kind, cd, k, t_dof, R, J, tg, U, Nw in wrench_cases(N):
+        rhs = wrench_rhs(M, k, t_dof, tg, U, Nw)
+        assert np.isfinite(rhs).all() and rhs.shape == (M, 1 + sum(t_dof) + k)
+        if kind.startswith("ints"):
+            AJ = np.array([sum(int(r) * t.astype(np.int64) for r, t in _wrench_terms(R, J, i, N)) for i in range(cd)])
+            out.append(([[mpf(int(v)) for v in row] for row in AJ @ rhs.astype(np.int64)], None))
+            continue
+        cols = [mpv(rhs[:, c]) for c in range(rhs.shape[1])]
+        acols = [[abs(v) for v in col] for col in cols]
+        D, Ab = [], []
+        for i in range(cd):
+            terms = [[mpf(float(r)) * v for v in mpv(t)] for r, t in _wrench_terms(R, J, i, N)]
+            row = [t0 + t1 + t2 for t0, t1, t2 in zip(*terms)]
+            arow = [abs(t0) + abs(t1) + abs(t2) for t0, t1, t2 in zip(*terms)]
+            D.append([mp.fdot(row, col) for col in cols])
+            Ab.append([mp.fdot(arow, col) for col in acols])
+        out.append((D, Ab))
+    return out
+
+
+def _wrench_unpack(o, build, N, cd, ncols, rec, tag):
+    """the footprint: guard words, operands bit for bit, nothing stored beyond the last tile (device) or outside cd x ncols (host);
+    returns the 12 x 32 block"""
+    M = N - 6
+    Rc, tg, U, Nw, Jb, wm, LDS = _wrench_offsets(N)
+    assert o.shape == (LDS,), (tag, o.shape)
+    blocks = ((Rc, 18), (Jb, 12 * N), (tg, M), (U, 24 * M), (Nw, 6 * M))  # (in the order of the input record)
+    guard = np.ones(LDS, bool)
+    guard[wm:wm + 384] = False
+    at = 0
+    for off, n in blocks:
+        guard[off:off + n] = False
+        assert _bits_equal(o[off:off + n], rec[at:at + n]), (tag, "an operand changed", off)
+        at += n
+    assert at == rec.size and np.isnan(o[guard]).all(), (tag, "guard words", np.flatnonzero(guard & ~np.isnan(o)))
+    W = o[wm:wm + 384].reshape(12, 32)
+    ntile = (ncols + 15) // 16
+    assert (W[:, 16 * ntile:] == probe.FRAME_SENTINEL).all(), (tag, "stored beyond the last tile")
+    if build == "emu":
+        assert (W[:, ncols:] == probe.FRAME_SENTINEL).all() and (W[cd:, :] == probe.FRAME_SENTINEL).all(), (tag, "host: stored outside cd x ncols")
+    return W
+
+
+def check_wrench(build, name, threads=64):
+    """wrench_maps<N, NT, Map> over every hierarchy: rows 0..cd-1 and columns 0..ncols-1 against the reference.  Rows 6..11 with one
+    contact are not asserted (the host leaves the sentinel, the device stores what the stale operands give); rows 0..5 must meet the
+    bars and be finite with NaN standing in R_1 and in rows 6..11 of Jbar^T"""
+    N = WRENCH_INSTS[name]
+    M = N - 6
+    cs, ref = wrench_cases(N), _wrench_ref(N)
+    assert len(cs) <= probe.MAX_B
+    din = np.stack([_wrench_record(N, *c[4:]) for c in cs])
+    o = probe.run(build, name, din, np.array([_wrench_ip(cd, k, t) for _, cd, k, t, *_ in cs]), threads)
+    g = gamma(M + 3)
+    worst = 0.0
+    for b, (kind, cd, k, t_dof, *_) in enumerate(cs):
+        ncols = 1 + sum(t_dof) + k
+        tag = f"{build} {name} t{threads} case {b} ({kind}, cd {cd}, k {k}, t {t_dof})"
+        W = _wrench_unpack(o[b], build, N, cd, ncols, din[b], tag)
+        base = kind.rstrip("1")
+        if kind.endswith("1"):
+            assert np.isfinite(W[:cd, :ncols]).all(), (tag, "a stale operand of the inactive contact reached rows 0..5")
+        worst = max(worst, _check_block(tag, base, W[:cd, :ncols], ref[b][0], ref[b][1], cd, ncols, g))
+    return dict(worst_u=worst, n=len(cs))
+
+
+def check_wrench_layout(build, threads=64, names=tuple(WRENCH_INSTS)):
+    """exhaustive layout sweep of wrench_maps: R and Jbar^T of distinct integers, the right-hand side e_c in exactly ONE column, for
+    every column and every c < M of the 31-column hierarchy and of (6, 0, [6, 3]).  That column of WM must be exactly column c of
+    A_rot Jbar[:, 6:], every other live column exactly zero: a transposed rotation, a swapped h / x split, a wrong stride or a level
+    off by one each move a number (the unaddressed words of U / NwJw hold NaN)"""
+    n = 0
+    for name in names:
+        N = WRENCH_INSTS[name]
+        M = N - 6
+        R = (1.0 + np.arange(18)).reshape(2, 3, 3)
+        J = (20.0 + np.arange(12 * N)).reshape(12, N)
+        J[:, :6] = np.nan
+        AJ = np.array([sum(r * t for r, t in _wrench_terms(R, J, i, N)) for i in range(12)])  # (12, M): integers far below 2^53, exact
+        for cd, k, t_dof in WRENCH_LAYOUT_HIER:
+            ncols = 1 + sum(t_dof) + k
+            # where column `col` lives: (block, level, column inside the block)
+            where = [("tg", 0, 0)] + [("U", l, j) for l, t in enumerate(t_dof) for j in range(t)] + [("N", 0, j) for j in range(k)]
+            assert len(where) == ncols
+            todo = [(col, c) for col in range(ncols) for c in range(M)]
+            for c0 in range(0, len(todo), probe.MAX_B):
+                part = todo[c0:c0 + probe.MAX_B]
+                recs = []
+                for col, c in part:
+                    tg, U, Nw = np.zeros(M), np.zeros((4, M, 6)), np.zeros((M, 6))
+                    _wrench_poison(M, cd, k, t_dof, U, Nw)
+                    blk, l, j = where[col]
+                    if blk == "tg":
+                        tg[c] = 1.0
+                    elif blk == "U":
+                        U[l][c, j] = 1.0
+                    else:
+                        Nw[c, j] = 1.0
+                    rhs = wrench_rhs(M, k, t_dof, tg, U, Nw)
+                    assert rhs.sum() == 1.0 and rhs[c, col] == 1.0
+                    recs.append(_wrench_record(N, R, J, tg, U, Nw))
+                din = np.stack(recs)
+                o = probe.run(build, name, din, np.array([_wrench_ip(cd, k, t_dof)] * len(part)), threads)
+                for b, (col, c) in enumerate(part):
+                    tag = f"{build} {name} t{threads} layout cd {cd} t {t_dof}: e_{c} in column {col}"
+                    W = _wrench_unpack(o[b], build, N, cd, ncols, din[b], tag)
+                    E = np.zeros((cd, ncols))
+                    E[:, col] = AJ[:cd, c]
+                    assert np.array_equal(W[:cd, :ncols], E), (tag, np.argwhere(W[:cd, :ncols] != E)[:8], W[:cd, col], AJ[:cd, c])
+                n += len(part)
+    return dict(n=n)
+
+
 def check_gc_refusals(build):
     import pytest
 
     for name, ip in (("pinv_cod12", [0]), ("pinv_cod12", [13]), ("gj_rows6", [7, 0]), ("gj_rows12", [0, 1]), ("gj_rows18", [19, 0]),
                      ("gj_rows18", [4, 2]), ("spd_scaled12", [0]), ("spd_scaled12", [13]), ("mmg_12_39_39_nn", [0, 1, 1]),
                      ("mmg_12_39_39_nn", [13, 39, 39]), ("mmg_12_12_39_nt", [12, 40, 12]), ("mmg_33_12_12_tn", [33, 12, 13]),
-                     ("mmg_12_33_12_nn", [12, 0, 33])):
+                     ("mmg_12_33_12_nn", [12, 0, 33]), ("gram_39", [0]), ("gram_23", [7]), ("gram_50", [13]),
+                     ("wrench_39", [12, 0, 2, 6, 3, 0, 0]), ("wrench_39", [6, 6, 2, 6, 3, 0, 0]), ("wrench_37", [0, 0, 1, 3, 0, 0, 0]),
+                     ("wrench_23", [12, 6, 0, 6, 3, 0, 0]), ("wrench_24", [12, 6, 5, 6, 6, 6, 6]), ("wrench_50", [12, 6, 2, 6, 4, 0, 0]),
+                     ("wrench_50", [6, 0, 1, 0, 3, 3, 3]), ("wrench_39", [12, 6, 4, 6, 6, 6, 12])):
         sz = probe.sizes(build, name)
         with pytest.raises(RuntimeError, match="outside"):
             probe.run(build, name, np.zeros((1, sz[0])), np.array([ip]))
@@ -1242,6 +1597,12 @@ def write_device_figures(path=DEV_FILE):
     for name in MMG_INSTS:
         r = both(lambda t: check_mmg("gpu", name, t))
         lines.append(f"{name}: worst error {max(x['worst_u'] for x in r):.3f} u |A||B| (bar gamma_(kk+1) <= ~ {MMG_INSTS[name][2] + 1})")
+    for name, N in GRAM_INSTS.items():
+        r = both(lambda t: check_gram("gpu", name, t))
+        lines.append(f"{name}: worst error {max(x['worst_u'] for x in r):.3f} u |Y||J^T| (bar gamma_{N + 3} ~ {N + 3})")
+    for name, N in WRENCH_INSTS.items():
+        r = both(lambda t: check_wrench("gpu", name, t))
+        lines.append(f"{name}: worst error {max(x['worst_u'] for x in r):.3f} u sum_c (|R||J|)_c |rhs_c| (bar gamma_{N - 3} ~ {N - 3})")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))

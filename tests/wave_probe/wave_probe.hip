@@ -70,6 +70,11 @@ const Inst kInst[] = {
     WP_GC("spd_reg33_rl", kInverse, 6, WpSpdReg<33, false>), WP_GC("spd_scaled12", kInverse, 7, WpSpdScaled),
     WP_GC("mmg_12_39_39_nn", kGemm, 8, WpMmg<12, 39, 39, 0>), WP_GC("mmg_12_12_39_nt", kGemm, 9, WpMmg<12, 12, 39, 1>),
     WP_GC("mmg_33_12_12_tn", kGemm, 10, WpMmg<33, 12, 12, 2>), WP_GC("mmg_12_33_12_nn", kGemm, 11, WpMmg<12, 33, 12, 0>),
+    // the two in-place matrix-core tiles of the cycle at the built-in size, two pack sizes, a size without K padding and the largest model
+    WP_GC("gram_39", kGemm, 12, WpGram<39>), WP_GC("gram_37", kGemm, 13, WpGram<37>), WP_GC("gram_23", kGemm, 14, WpGram<23>),
+    WP_GC("gram_24", kGemm, 15, WpGram<24>), WP_GC("gram_50", kGemm, 16, WpGram<50>),
+    WP_GC("wrench_39", kGemm, 17, WpWrench<39>), WP_GC("wrench_37", kGemm, 18, WpWrench<37>), WP_GC("wrench_23", kGemm, 19, WpWrench<23>),
+    WP_GC("wrench_24", kGemm, 20, WpWrench<24>), WP_GC("wrench_50", kGemm, 21, WpWrench<50>),
 };
 constexpr int kNInst = (int)(sizeof(kInst) / sizeof(kInst[0]));
 constexpr int kMaxB = 512;

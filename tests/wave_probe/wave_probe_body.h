@@ -5,7 +5,8 @@
 // The probe includes the shipped headers and calls the shipped functions; it holds no copy of any of them, and nothing of it is
 // linked into libdwbc_hip.so.  Included once per arithmetic type: wave_probe.hip (double, every family) and wave_probe_f32.hip
 // (WAVE_PROBE_F32: DWBC_REAL = float, namespace renamed; the cross-lane primitives and the scalar routines -- wave_gemm, the LDS-fed
-// sweeps and the batched row products are fp64-only on the device, their fp32 build takes the same plain code as the host).
+// sweeps, the batched row products and the two matrix-core tiles of the cycle, contact_gram and wrench_maps, are fp64-only on the
+// device, their fp32 build takes the same plain code as the host).
 //
 // A family is a struct: NIN doubles and NIP ints in, NOUT doubles out per problem, LDS reals of scratch per wave (even: every wave's
 // slice and every operand in it starts at a 16-byte boundary, as the kernels place theirs), check(ip) for the run-time sizes and
@@ -532,6 +533,106 @@ struct WpMmg {
         WSYNC();
         LANES {
             for (int e = lane; e < SC; e += 64) out[e] = (double)L[oC + e];
+        }
+    }
+};
+// ---- 7. the two in-place matrix-core tiles of the cycle (dwbc_cycle2.h): contact_gram (stage 1 of every cycle kernel, the
+// redistribution and the gravity-compensation kernels) and wrench_maps (the cascade).  fp64 only: on the device the fp32 build takes the
+// plain loops of the host.  Instantiated in wave_probe_gc.hip.  Every block sits at a 16-byte aligned offset with two NaN words in
+// front of it and behind it (and one more where its length is odd); the output block is pre-filled with the frame sentinel.
+// out (both families): the wave's WHOLE slice of LDS after the call -- guards, operands as they read back, the output block.
+
+// contact_gram<N, 12, NT, OUT>.  ip: cd (6 or 12).  in: Yt then JCt, each N x 12 (rows of the transposed blocks; the caller keeps the
+// entries of the rows >= cd of Y / J_C, i.e. columns >= cd here, zero: the function's contract)
+template <int N>
+struct WpGram {
+    static constexpr int C = 12;
+    static constexpr int oY = 2, oJ = oY + N * C + 2, oO = oJ + N * C + 2, LDS = oO + C * C + 2;
+    static constexpr int NIN = 2 * N * C, NIP = 1, NOUT = LDS;
+    static_assert(oY % 2 == 0 && oJ % 2 == 0 && oO % 2 == 0 && LDS % 2 == 0, "16-byte aligned blocks");
+    static const char *check(const int *ip) { return (ip[0] != 6 && ip[0] != 12) ? "cd outside {6, 12}" : nullptr; }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int cd = wp_uni(ip[0]);
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= oO && e < oO + C * C) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            for (int e = lane; e < N * C; e += 64) L[oY + e] = (real_t)in[e], L[oJ + e] = (real_t)in[N * C + e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        contact_gram<N, C, kWpNT, oO>(WP_THR, L + oY, L + oJ, cd, L);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < LDS; e += 64) out[e] = (double)L[e];
+        }
+    }
+};
+
+// wrench_maps<N, NT, Map> with an LDS map of the probe's own: nothing but the members the function reads.
+// ip: cd, k ((12, 6) or (6, 0)), n_levels (1..4), t_dof[4] (3 or 6 each; beyond n_levels ignored); 1 + sum t + k <= 31 columns.
+// The Setup is built here from ip: n_levels, fstar_off[] and fstar_total, the only members the function reads.
+// in: R_0, R_1 (18), JbT (12 x N), tg (M), U (4 levels x M x 6), NwJw (M x 6)
+template <int N>
+struct WpWrenchMap {
+    static constexpr int M = N - 6, T = 6, WLD = 32, C = 12;
+    static constexpr int Rc = 2, tg = Rc + 18 + 2, U = tg + wp_ev(M) + 2, NwJw = U + kMaxLevels * M * T + 2;
+    static constexpr int JbT = NwJw + M * 6 + 2, wm = JbT + C * N + 2, total = wm + C * WLD + 2;
+    static_assert(Rc % 2 == 0 && tg % 2 == 0 && U % 2 == 0 && NwJw % 2 == 0 && JbT % 2 == 0 && wm % 2 == 0 && total % 2 == 0, "16-byte aligned blocks");
+};
+template <int N>
+struct WpWrench {
+    using S = WpWrenchMap<N>;
+    static constexpr int M = S::M, C = S::C;
+    static constexpr int LDS = S::total;
+    static constexpr int NIN = 18 + C * N + M + kMaxLevels * M * S::T + M * 6, NIP = 3 + kMaxLevels, NOUT = LDS;
+    static const char *check(const int *ip) {
+        if (!((ip[0] == 12 && ip[1] == 6) || (ip[0] == 6 && ip[1] == 0))) return "(cd, k) outside {(12, 6), (6, 0)}";
+        if (ip[2] < 1 || ip[2] > kMaxLevels) return "n_levels outside 1..4";
+        int ftot = 0;
+        for (int l = 0; l < ip[2]; l++) {
+            if (ip[3 + l] != 3 && ip[3 + l] != 6) return "t_dof outside {3, 6}";
+            ftot += ip[3 + l];
+        }
+        return 1 + ftot + ip[1] > 31 ? "1 + sum t_dof + k outside 1..31" : nullptr;
+    }
+    DWBC_WDEV static void problem(const double *in, const int *ip, double *out, real_t *L) {
+        DWBC_LANE_DECL;
+        const int cd = wp_uni(ip[0]), k = wp_uni(ip[1]);
+        Setup su;  // (only what wrench_maps reads is set)
+        su.n_levels = wp_uni(ip[2]);
+        int off = 0;
+        for (int l = 0; l < kMaxLevels; l++) {
+            su.fstar_off[l] = off;
+            off += l < su.n_levels ? wp_uni(ip[3 + l]) : 0;
+        }
+        su.fstar_total = off;
+        LANES {
+            for (int e = lane; e < LDS; e += 64) L[e] = (e >= S::wm && e < S::wm + C * S::WLD) ? (real_t)kWpSentinel : WP_NAN;
+        }
+        WSYNC();
+        LANES {
+            const double *p = in;
+            for (int e = lane; e < 18; e += 64) L[S::Rc + e] = (real_t)p[e];
+            p += 18;
+            for (int e = lane; e < C * N; e += 64) L[S::JbT + e] = (real_t)p[e];
+            p += C * N;
+            for (int e = lane; e < M; e += 64) L[S::tg + e] = (real_t)p[e];
+            p += M;
+            for (int e = lane; e < kMaxLevels * M * S::T; e += 64) L[S::U + e] = (real_t)p[e];
+            p += kMaxLevels * M * S::T;
+            for (int e = lane; e < M * 6; e += 64) L[S::NwJw + e] = (real_t)p[e];
+        }
+        WSYNC();
+        DWBC_SYNC();
+        wrench_maps<N, kWpNT, S>(WP_THR, su, L, L + S::JbT, cd, k, L + S::wm);
+        DWBC_SYNC();
+        WSYNC();
+        LANES {
+            for (int e = lane; e < LDS; e += 64) out[e] = (double)L[e];
         }
     }
 };

@@ -1,5 +1,5 @@
 // wave_probe_gc.hip -- TEST HARNESS ONLY: the probe's instantiations of the general-contact kernel's routines (gj_inverse_rows,
-// spd_inverse_reg, spd_inverse_scaled, mmg of dwbc_cycle_gc.h) and of pinv_cod_small / qr_small (dwbc_cycle2.h), in a translation
+// spd_inverse_reg, spd_inverse_scaled, mmg of dwbc_cycle_gc.h) and of pinv_cod_small / qr_small, contact_gram and wrench_maps (dwbc_cycle2.h), in a translation
 // unit of their own: the 39- and 33-wide register sweeps compile beside the others (the namespace is renamed so that the units link).
 #ifndef DWBC_HOST_EMU
 #include <hip/hip_runtime.h>
@@ -25,6 +25,16 @@ extern "C" const char *wave_probe_run_gc(int kind, const void *args, int threads
     case 9: return wp_run<WpMmg<12, 12, 39, 1>>(a, threads);
     case 10: return wp_run<WpMmg<33, 12, 12, 2>>(a, threads);
     case 11: return wp_run<WpMmg<12, 33, 12, 0>>(a, threads);
+    case 12: return wp_run<WpGram<39>>(a, threads);
+    case 13: return wp_run<WpGram<37>>(a, threads);
+    case 14: return wp_run<WpGram<23>>(a, threads);
+    case 15: return wp_run<WpGram<24>>(a, threads);
+    case 16: return wp_run<WpGram<50>>(a, threads);
+    case 17: return wp_run<WpWrench<39>>(a, threads);
+    case 18: return wp_run<WpWrench<37>>(a, threads);
+    case 19: return wp_run<WpWrench<23>>(a, threads);
+    case 20: return wp_run<WpWrench<24>>(a, threads);
+    case 21: return wp_run<WpWrench<50>>(a, threads);
     }
     return "general-contact kind out of range";
 }
