@@ -387,6 +387,56 @@ const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b);
 /* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
 int dwbc_batch_time_dynamics(dwbc_batch *b, int steps, float *ms);
 
+/* ---- SetContact + CalcContactConstraint as a call of its own (reference include/dwbc.h:432-474, src/dwbc.cpp:433-478,
+ * src/wbd.cpp:108-143): the contact-space members a caller reads off RobotData between UpdateKinematics and SetTaskSpace (the reference's
+ * harnesses: J_t A_inv_ N_C for a task acceleration, J_C^T f in an inverse-dynamics check; tests/dwbc_test.cpp:92-113 pins seven of them)
+ * in one lean kernel: stage 0 of the cycle, its contact stage, the NwJw closed form and the W^+ sweep.  No task level, no gravity vector,
+ * no QP.  The caller asks for a set of outputs; what is not asked for is not computed: only J_C and / or the contact frames -- no A^-1
+ * sweep; none of A_INV_N_C, W, W_INV -- the columns are never updated to A^-1 N_c; no W_INV -- no W + alpha P and no 33-pivot sweep;
+ * neither NWJW nor W_INV -- no internal-wrench basis; no N_C -- no n x n product.  Outputs (buffer slots of their own, no dwbc_field;
+ * batch-major; the shapes are fixed whatever the support, zero beyond the active contact dof cd; m = n - 6):
+ *   DWBC_CS_J_C (12, n) f64          J_C               src/dwbc.cpp:445-453
+ *   DWBC_CS_LAMBDA_C (12, 12) f64    Lambda_contact    src/wbd.cpp:115   row stride 12, zero outside cd x cd (the dump field DWBC_LAMBDA_C has stride cd)
+ *   DWBC_CS_J_C_INV_T (12, n) f64    J_C_INV_T         src/wbd.cpp:116
+ *   DWBC_CS_N_C (n, n) f64           N_C               src/wbd.cpp:117
+ *   DWBC_CS_A_INV_N_C (n, n) f64     A_inv_N_C         src/wbd.cpp:118
+ *   DWBC_CS_W (m, m) f64             W                 src/wbd.cpp:119
+ *   DWBC_CS_W_INV (m, m) f64         W_inv             src/wbd.cpp:124, 140
+ *   DWBC_CS_NWJW (m, 6) f64          NwJw              src/wbd.cpp:128   zero on one foot (k = 0)
+ *   DWBC_CS_CONTACT_POS (2, 3) f64   cc_[i].xc_pos     in the order of the active contacts, as DWBC_CONTACT_POS
+ *   DWBC_CS_CONTACT_ROT (2, 9) f64   cc_[i].rotm
+ *   DWBC_CS_STATUS (1) i32           return value of CalcContactConstraint; always written
+ * Support: both feet (k = 6); one foot (k = 0: W has full rank, W_inv is its inverse); no active contact (N_C = I, A_inv_N_C = A_inv,
+ * W its joint block, W_inv that block's inverse, every contact-sized output zero, status 1).  More flags set than two (device-resident
+ * flags), a failed Lambda_c or a bad pivot of the W sweep: status 0 and every asked-for output of that instance zero.
+ * The launch reads the state, the model, the registered contacts and the flags: it needs no task space, reads no f*, torque limit or
+ * per-instance parameter record, and names no buffer of dwbc_batch_solve, dwbc_batch_redistribute, dwbc_batch_grav_compensation,
+ * dwbc_batch_update_kinematics or dwbc_batch_update_dynamics -- the six may be called on one batch in any order.
+ * Refused (dwbc_last_error), in this order, before anything is launched: DWBC_F32 batches; dwbc_batch_set_max_active_contacts above 2; a
+ * model without the kernel (built in for TOCABI's size on its own tree and on any; every kernel pack carries its size's); a batch without a
+ * registered contact -- all four at dwbc_batch_set_contact_space_outputs already.  Further: an unknown bit; a launch without a request;
+ * get / bind of an output that was not asked for; dwbc_batch_get_contact_space before the first launch of the request.
+ * Not built: three contacts, fp32, the reduced system's matrices, V2 (the device forms NwJw in closed form and has no COD basis), P_C (an
+ * output of the gravity launch's arithmetic); the facade include/dwbc_amd.hpp keeps serving these members from its cycle. */
+enum dwbc_contact_space_output {
+    DWBC_CS_J_C = 0, DWBC_CS_LAMBDA_C = 1, DWBC_CS_J_C_INV_T = 2, DWBC_CS_N_C = 3, DWBC_CS_A_INV_N_C = 4, DWBC_CS_W = 5, DWBC_CS_W_INV = 6,
+    DWBC_CS_NWJW = 7, DWBC_CS_CONTACT_POS = 8, DWBC_CS_CONTACT_ROT = 9, DWBC_CS_STATUS = 10
+};
+/* mask: bits 1u << dwbc_contact_space_output; DWBC_CS_STATUS is implied.  0 drops the request and its buffers.  A new request gets output
+ * buffers of its own: bound ones are let go of (bind again), earlier results are gone. */
+int dwbc_batch_set_contact_space_outputs(dwbc_batch *b, unsigned mask);
+/* SetContact (with the flags of dwbc_batch_set_contact, or device-bound DWBC_IN_CONTACT) + CalcContactConstraint; asynchronous on the
+ * batch's stream; uploads newer host mirrors of q and the contact flags first, like a solve */
+int dwbc_batch_calc_contact_constraint(dwbc_batch *b);
+size_t dwbc_batch_contact_space_bytes(const dwbc_batch *b, int what);  /* of all B instances; 0: not asked for, no such output */
+int dwbc_batch_get_contact_space(dwbc_batch *b, int what, void *host_out, size_t bytes);  /* synchronises the stream */
+/* zero-copy: a caller-owned DEVICE buffer of dwbc_batch_contact_space_bytes(b, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_contact_space(dwbc_batch *b, int what, void *device_ptr);
+/* name of the kernel dwbc_batch_calc_contact_constraint launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b);
+/* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_contact_space(dwbc_batch *b, int steps, float *ms);
+
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least
  * squares), optional cost 1/2 y^T H y; levels are solved in sequence inside the null space of the earlier equalities.  The

@@ -117,6 +117,14 @@ SYMBOLS = [
     ("dwbc_batch_bind_dynamics", _i, [_vp, _i, _vp]),
     ("dwbc_batch_dynamics_kernel_name", C.c_char_p, [_vp]),
     ("dwbc_batch_time_dynamics", _i, [_vp, _i, C.POINTER(C.c_float)]),
+    # SetContact + CalcContactConstraint (J_C, Lambda_contact, J_C_INV_T, N_C, A_inv_N_C, W, W_inv, NwJw, contact frames) in a launch of its own
+    ("dwbc_batch_set_contact_space_outputs", _i, [_vp, C.c_uint]),
+    ("dwbc_batch_calc_contact_constraint", _i, [_vp]),
+    ("dwbc_batch_contact_space_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_batch_get_contact_space", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_bind_contact_space", _i, [_vp, _i, _vp]),
+    ("dwbc_batch_contact_space_kernel_name", C.c_char_p, [_vp]),
+    ("dwbc_batch_time_contact_space", _i, [_vp, _i, C.POINTER(C.c_float)]),
     # link poses, velocities and Jacobians in a launch of their own
     ("dwbc_batch_set_link_query", _i, [_vp, _i, _vp, _vp, _i]),
     ("dwbc_batch_update_kinematics", _i, [_vp]),

@@ -15,6 +15,8 @@
     wbc.link_states()["rot"]
     wbc.set_dynamics_outputs(["A", "B", "CMM"]); wbc.update_dynamics()   # the dynamics half of UpdateKinematics: rd_.A_ / A_inv_ / B_ / G_ / CMM_
     wbc.dynamics()["A"]
+    wbc.set_contact_space_outputs(["N_C", "A_inv_N_C", "J_C"]); wbc.calc_contact_constraint()   # SetContact + CalcContactConstraint: the contact space
+    wbc.contact_space()["N_C"]
 
 All arithmetic happens in libdwbc_hip.so (hand-written HIP, gfx950).  torch is only used, optionally, to own
 device buffers and streams (bind_tensor) and for torch.distributed in bench.py.
@@ -33,6 +35,9 @@ SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
 REDIST_ADD_GRAVITY = 8  # a bit of the redistribution entry points' flags
 GRAV_OUTPUTS = {"tau": 0, "wrench": 1, "status": 2}  # enum dwbc_grav_output
 LINK_QUERY_OUTPUTS = {"pos": 0, "rot": 1, "vel": 2, "jac": 3}  # enum dwbc_link_query_output
+# enum dwbc_contact_space_output
+CONTACT_SPACE_OUTPUTS = {"J_C": 0, "Lambda_c": 1, "J_C_INV_T": 2, "N_C": 3, "A_inv_N_C": 4, "W": 5, "W_inv": 6, "NwJw": 7, "contact_pos": 8, "contact_rot": 9,
+                         "status": 10}
 DYNAMICS_OUTPUTS = {"A": 0, "A_inv": 1, "B": 2, "G": 3, "CMM": 4, "com": 5, "status": 6}  # enum dwbc_dynamics_output
 
 
@@ -580,6 +585,70 @@ class Batch:
     def time_dynamics(self, steps):
         ms = C.c_float(0)
         _check(self._L.dwbc_batch_time_dynamics(self._h, int(steps), C.byref(ms)))
+        return ms.value
+
+    # ---- SetContact + CalcContactConstraint on their own: the contact-space members of RobotData (reference src/dwbc.cpp:433-478, src/wbd.cpp:108-143)
+    def set_contact_space_outputs(self, names):
+        """The outputs calc_contact_constraint() writes: any of "J_C" (12, n), "Lambda_c" (12, 12), "J_C_INV_T" (12, n), "N_C" (n, n),
+        "A_inv_N_C" (n, n), "W" (m, m), "W_inv" (m, m), "NwJw" (m, 6), "contact_pos" (2, 3), "contact_rot" (2, 3, 3); "status" is always
+        written.  The shapes are fixed whatever the support: zero beyond the active contact dof.  What is not asked for is not computed: only
+        "J_C" / the frames, no A^-1 sweep; no "W_inv", no 33-pivot sweep; no "N_C", no n x n product.  An empty list drops the request and its
+        buffers.  A new request has new output buffers: bind tensors after it."""
+        mask = 0
+        for k in names:
+            mask |= 1 << CONTACT_SPACE_OUTPUTS[k]
+        _check(self._L.dwbc_batch_set_contact_space_outputs(self._h, mask))
+        for k in CONTACT_SPACE_OUTPUTS:
+            self._keep.pop("contact_space_" + k, None)
+
+    def calc_contact_constraint(self):
+        """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA, the contact stage and what the request asks for, from the
+        state and the contact flags (set_contact, or flags bound on the device).  Needs no task space, and leaves every output of solve(),
+        redistribute(), grav_compensation(), update_kinematics() and update_dynamics() as it is; the six may be called in any order."""
+        _check(self._L.dwbc_batch_calc_contact_constraint(self._h))
+
+    def _contact_space_shape(self, name):
+        n, m, B = self.n, self.n - 6, self.B
+        return {"J_C": ((B, 12, n), np.float64), "Lambda_c": ((B, 12, 12), np.float64), "J_C_INV_T": ((B, 12, n), np.float64), "N_C": ((B, n, n), np.float64),
+                "A_inv_N_C": ((B, n, n), np.float64), "W": ((B, m, m), np.float64), "W_inv": ((B, m, m), np.float64), "NwJw": ((B, m, 6), np.float64),
+                "contact_pos": ((B, 2, 3), np.float64), "contact_rot": ((B, 2, 3, 3), np.float64), "status": ((B,), np.int32)}[name]
+
+    def contact_space(self):
+        """dict of the asked-for outputs and ``status`` (B,) int32 (the return value of CalcContactConstraint; 0: that instance's outputs
+        are zero) of the last calc_contact_constraint(); synchronises the stream"""
+        out = {}
+        for name, what in CONTACT_SPACE_OUTPUTS.items():
+            if self._L.dwbc_batch_contact_space_bytes(self._h, what) == 0 and name != "status":
+                continue
+            shape, dt = self._contact_space_shape(name)
+            a = np.zeros(shape, dt)
+            _check(self._L.dwbc_batch_get_contact_space(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def bind_contact_space(self, name, tensor):
+        """asked-for output ``name`` of calc_contact_constraint() into a caller-owned device tensor (float64; "status": int32), written in
+        place by every later launch; None: back to a buffer of the batch's own"""
+        what = CONTACT_SPACE_OUTPUTS[name]
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_contact_space(self._h, what, None))
+            self._keep.pop("contact_space_" + name, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = self._L.dwbc_batch_contact_space_bytes(self._h, what)
+        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(self._L.dwbc_batch_bind_contact_space(self._h, what, C.c_void_p(tensor.data_ptr())))
+        self._keep["contact_space_" + name] = tensor
+
+    def contact_space_kernel_name(self):
+        name = self._L.dwbc_batch_contact_space_kernel_name(self._h).decode()
+        if not name:
+            raise DwbcError(_lib.last_error())
+        return name
+
+    def time_contact_space(self, steps):
+        ms = C.c_float(0)
+        _check(self._L.dwbc_batch_time_contact_space(self._h, int(steps), C.byref(ms)))
         return ms.value
 
     def time_solves(self, steps, reduced=False):

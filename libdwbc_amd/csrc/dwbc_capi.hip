@@ -226,6 +226,7 @@ static dwbc_plan::Request plan_request(const dwbc_batch *b, bool reduced) {
     q.n_cu = b->n_cu;
     q.reduced = reduced;
     q.max_active = b->max_active;
+    q.n_contacts = b->su.n_contacts;
     q.wide_tasks = setup_wide_tasks(b->su);
     q.hqp = b->hqp != 0;
     q.warm = b->warm != 0;
@@ -1325,6 +1326,155 @@ int dwbc_batch_bind_dynamics(dwbc_batch *b, int what, void *p) {
 const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b) {
     static thread_local char name[160];
     const dwbc_plan::Plan p = dynamics_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
+
+// ---- SetContact + CalcContactConstraint on their own (J_C, Lambda_contact, J_C_INV_T, N_C, A_inv_N_C, W, W_inv, NwJw, contact frames):
+// the lean kernel of dwbc_contact_space.h
+static_assert(kCsJC == 1u << DWBC_CS_J_C && kCsLambda == 1u << DWBC_CS_LAMBDA_C && kCsJCInvT == 1u << DWBC_CS_J_C_INV_T && kCsNC == 1u << DWBC_CS_N_C &&
+                  kCsAInvNC == 1u << DWBC_CS_A_INV_N_C && kCsW == 1u << DWBC_CS_W && kCsWInv == 1u << DWBC_CS_W_INV && kCsNwJw == 1u << DWBC_CS_NWJW &&
+                  kCsPos == 1u << DWBC_CS_CONTACT_POS && kCsRot == 1u << DWBC_CS_CONTACT_ROT, "CsIO::mask is 1u << dwbc_contact_space_output");
+static dwbc_plan::Plan contact_space_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.contact_space = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+
+// bytes of all B instances of one output under a request (0: not part of it, no such output)
+static size_t contact_space_bytes(const dwbc_batch *b, unsigned mask, int what) {
+    if (what < DWBC_CS_J_C || what > DWBC_CS_STATUS || !((mask >> what) & 1u)) return 0;
+    const size_t n = (size_t)b->n, m = n - 6, d = sizeof(double);
+    const size_t per[11] = {12 * n * d, 144 * d, 12 * n * d, n * n * d, n * n * d, m * m * d, m * m * d, m * 6 * d, 6 * d, 18 * d, sizeof(int)};
+    return (size_t)b->B * per[what];
+}
+
+size_t dwbc_batch_contact_space_bytes(const dwbc_batch *b, int what) { return contact_space_bytes(b, b->cs_mask, what); }
+
+int dwbc_batch_set_contact_space_outputs(dwbc_batch *b, unsigned mask) {
+    constexpr unsigned kAll = (1u << (DWBC_CS_STATUS + 1)) - 1u;
+    if (mask & ~kAll) return fail("contact space: unknown output bit (the outputs are 1u << DWBC_CS_J_C .. 1u << DWBC_CS_STATUS)");
+    if (mask) {
+        const dwbc_plan::Plan p = contact_space_plan(b);
+        if (!p.row) return fail(p.err);
+        mask |= 1u << DWBC_CS_STATUS;
+    }
+    // outputs of the new request, owned by the batch; allocated here, so that dwbc_batch_calc_contact_constraint itself allocates nothing
+    HIP_OK(hipSetDevice(b->device));
+    for (int w = DWBC_CS_J_C; w <= DWBC_CS_STATUS; w++) release(b->buf[fld::kCoJC + w]);  // (hipFree waits for the launches that write them)
+    b->cs_mask = mask;
+    b->cs_ran = false;
+    for (int w = DWBC_CS_J_C; w <= DWBC_CS_STATUS; w++)
+        if (const size_t bytes = dwbc_batch_contact_space_bytes(b, w))
+            if (!ensure(b->buf[fld::kCoJC + w], bytes)) return 0;
+    return 1;
+}
+
+static int launch_contact_space(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    const void *fn = p.row->fn;
+    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        b->lds_attr_set.push_back(fn);
+    }
+    BatchIO io{};  // the state, the flags and the model; no buffer of the cycle or of the other lean launches is named
+    io.B = b->B;
+    io.q = b->dev<double>(fld::kQ);
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.body = b->d_body;
+    io.topo = b->d_topo;
+    io.hqp = 1;
+    io.pair_swap_bit = -1;
+    CsIO cio{};
+    cio.mask = b->cs_mask & ~(1u << DWBC_CS_STATUS);
+    cio.J_C = b->dev<double>(fld::kCoJC);
+    cio.Lambda_c = b->dev<double>(fld::kCoLambda);
+    cio.J_C_INV_T = b->dev<double>(fld::kCoJCInvT);
+    cio.N_C = b->dev<double>(fld::kCoNC);
+    cio.A_inv_N_C = b->dev<double>(fld::kCoAInvNC);
+    cio.W = b->dev<double>(fld::kCoW);
+    cio.W_inv = b->dev<double>(fld::kCoWInv);
+    cio.NwJw = b->dev<double>(fld::kCoNwJw);
+    cio.pos = b->dev<double>(fld::kCoPos);
+    cio.rot = b->dev<double>(fld::kCoRot);
+    cio.status = b->dev<int>(fld::kCoStatus);
+    void *args[] = {(void *)&b->su, (void *)&io, (void *)&cio};
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    b->cs_ran = true;
+    return 1;
+}
+
+// uploads whatever is pending of the state and the flags, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+static int contact_space_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
+    const dwbc_plan::Plan p = contact_space_plan(b);
+    if (!p.row) return fail(p.err);
+    if (!b->cs_mask) return fail("no contact-space request: call dwbc_batch_set_contact_space_outputs first");
+    HIP_OK(hipSetDevice(b->device));
+    bool queued = false;
+    for (const int slot : {fld::kQ, fld::kFlags})
+        if (!send(b, slot, &queued)) return 0;
+    if (queued && !mark_upload(b)) return 0;
+    if (!b->buf[fld::kFlags].d) return fail("no contact flags: call dwbc_batch_set_contact (or bind DWBC_IN_CONTACT) first");
+    if (planned) *planned = p;
+    return launch_contact_space(b, p);
+}
+
+int dwbc_batch_calc_contact_constraint(dwbc_batch *b) { return contact_space_once(b, nullptr); }
+
+int dwbc_batch_time_contact_space(dwbc_batch *b, int steps, float *ms) {
+    HIP_OK(hipSetDevice(b->device));
+    dwbc_plan::Plan p{};
+    if (!contact_space_once(b, &p)) return 0;  // uploads + warm launch
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&]() -> int {
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, b->stream));
+        for (int i = 0; i < steps; i++)
+            if (!launch_contact_space(b, p)) return 0;
+        HIP_OK(hipEventRecord(e1, b->stream));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(ms, e0, e1));
+        return 1;
+    };
+    const int ok = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+
+// why output `what` of the request cannot be named (nullptr: it can)
+static const char *contact_space_refusal(const dwbc_batch *b, int what) {
+    if (what < DWBC_CS_J_C || what > DWBC_CS_STATUS) return "contact space: unknown output";
+    if (!b->cs_mask) return "no contact-space request: call dwbc_batch_set_contact_space_outputs first";
+    if (!((b->cs_mask >> what) & 1u)) return "contact space: this output was not asked for (dwbc_batch_set_contact_space_outputs)";
+    return nullptr;
+}
+
+int dwbc_batch_get_contact_space(dwbc_batch *b, int what, void *out, size_t bytes) {
+    if (const char *why = contact_space_refusal(b, what)) return fail(why);
+    if (!b->cs_ran) return fail("no contact-space output yet: call dwbc_batch_calc_contact_constraint first");
+    const size_t need = dwbc_batch_contact_space_bytes(b, what);
+    if (bytes < need) return fail("output buffer too small");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kCoJC + what].d, out, need);
+}
+
+int dwbc_batch_bind_contact_space(dwbc_batch *b, int what, void *p) {
+    if (const char *why = contact_space_refusal(b, what)) return fail(why);
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kCoJC + what];
+    release(u);
+    b->cs_ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, dwbc_batch_contact_space_bytes(b, what));
+    u.d = p;
+    return 1;
+}
+
+const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = contact_space_plan(b);
     if (!p.row) { fail(p.err); return ""; }
     dwbc_plan::format_name(*p.row, name, sizeof name);
     return name;

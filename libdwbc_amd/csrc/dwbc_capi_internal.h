@@ -129,6 +129,10 @@ struct dwbc_batch {
     // whether a launch has filled the outputs
     unsigned dyn_mask = 0;
     bool dyn_ran = false;
+    // the contact-space request (dwbc_batch_set_contact_space_outputs): bits 1u << dwbc_contact_space_output with DWBC_CS_STATUS set
+    // (0: none), and whether a launch has filled the outputs
+    unsigned cs_mask = 0;
+    bool cs_ran = false;
     dwbc::DumpLayout dl{};
 };
 

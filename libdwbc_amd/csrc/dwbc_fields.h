@@ -13,9 +13,13 @@ using namespace dwbc;
 
 // device buffers of a batch that are owned or bound, sized once and uploaded from a host mirror if they have one: the bindable fields,
 // the diagnostics record, and the inputs that are no field -- the task-reference inputs and the per-instance parameter record
-// and the four outputs of a link query, the three of a gravity compensation and the seven of a dynamics launch, which are no field either (dwbc_batch::buf is indexed by this)
+// and the four outputs of a link query, the three of a gravity compensation the seven of a dynamics launch and the eleven of a contact-space launch, which are no field either (dwbc_batch::buf is indexed by this)
 enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kInstPar,
-            kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kDyA, kDyAInv, kDyB, kDyG, kDyCmm, kDyCom, kDyStatus, kSlotCount };
+            kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kDyA, kDyAInv, kDyB, kDyG, kDyCmm, kDyCom, kDyStatus,
+            kCoJC, kCoLambda, kCoJCInvT, kCoNC, kCoAInvNC, kCoW, kCoWInv, kCoNwJw, kCoPos, kCoRot, kCoStatus, kSlotCount };
+static_assert(kCoLambda == kCoJC + DWBC_CS_LAMBDA_C && kCoJCInvT == kCoJC + DWBC_CS_J_C_INV_T && kCoNC == kCoJC + DWBC_CS_N_C && kCoAInvNC == kCoJC + DWBC_CS_A_INV_N_C &&
+                  kCoW == kCoJC + DWBC_CS_W && kCoWInv == kCoJC + DWBC_CS_W_INV && kCoNwJw == kCoJC + DWBC_CS_NWJW && kCoPos == kCoJC + DWBC_CS_CONTACT_POS &&
+                  kCoRot == kCoJC + DWBC_CS_CONTACT_ROT && kCoStatus == kCoJC + DWBC_CS_STATUS, "kCoJC + dwbc_contact_space_output");
 static_assert(kDyAInv == kDyA + DWBC_DYN_A_INV && kDyB == kDyA + DWBC_DYN_B && kDyG == kDyA + DWBC_DYN_G && kDyCmm == kDyA + DWBC_DYN_CMM &&
                   kDyCom == kDyA + DWBC_DYN_COM && kDyStatus == kDyA + DWBC_DYN_STATUS, "kDyA + dwbc_dynamics_output");
 static_assert(kGvWrench == kGvTau + DWBC_GRAV_WRENCH && kGvStatus == kGvTau + DWBC_GRAV_STATUS, "kGvTau + dwbc_grav_output");

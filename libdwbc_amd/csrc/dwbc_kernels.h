@@ -13,6 +13,7 @@
 #include "dwbc_redistribute.h"
 #include "dwbc_link_query.h"
 #include "dwbc_dynamics.h"
+#include "dwbc_contact_space.h"
 
 namespace dwbc {
 
@@ -135,6 +136,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
     dynamics_instance<N, NB, 64, Topo>(th, su, io, dio, inst, lds);
 }
 
+// SetContact + CalcContactConstraint in a launch of its own (dwbc_contact_space.h): stage 0, the contact stage and, each behind a
+// wave-uniform branch on CsIO::mask, N_C, A^-1 N_c / W, the NwJw closed form and the W^+ sweep -- the redistribution kernel's LDS map,
+// register-capped like the other lean kernels: eight workgroups per CU
+template <int N, int NB, class Topo>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_contact_space_kernel(const Setup su, const BatchIO io, const CsIO cio) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    contact_space_instance<N, NB, 64, Topo>(th, su, io, cio, inst, lds);
+}
+
 #define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
@@ -205,6 +218,13 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_DYNAMICS(N, NB, TOPO, TK) \
     DWBC_ROW(N, NB, 0, TK, kDynamics, 0u, (LdsDyn<N, NB>::total_bytes), kNT, dwbc_dynamics_kernel, N, NB, dwbc::TOPO),
 #endif
+// the contact-space kernel: fp64 (DWBC_NO_CONTACT_SPACE_KERNEL: fp32), for a constant tree or any tree of the size; every kernel pack carries its own
+#ifdef DWBC_NO_CONTACT_SPACE_KERNEL
+#define DWBC_ROW_CONTACT_SPACE(N, NB, TOPO, TK)
+#else
+#define DWBC_ROW_CONTACT_SPACE(N, NB, TOPO, TK) \
+    DWBC_ROW(N, NB, 0, TK, kContactSpace, 0u, (LdsCs<N, NB>::total_bytes), kNT, dwbc_contact_space_kernel, N, NB, dwbc::TOPO),
+#endif
 // instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
 // and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
 // model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
@@ -228,6 +248,7 @@ const lp::Row kRows[] = {
     DWBC_ROW_GRAVCOMP(39, 34, TopoTocabi, 1) DWBC_ROW_GRAVCOMP(39, 34, TopoGeneric, 0)
     DWBC_ROW_LINK_QUERY(39, 34)
     DWBC_ROW_DYNAMICS(39, 34, TopoTocabi, 1) DWBC_ROW_DYNAMICS(39, 34, TopoGeneric, 0)
+    DWBC_ROW_CONTACT_SPACE(39, 34, TopoTocabi, 1) DWBC_ROW_CONTACT_SPACE(39, 34, TopoGeneric, 0)
 };
 #endif
 

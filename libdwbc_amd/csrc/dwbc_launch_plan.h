@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation or the dynamics of UpdateKinematics):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation, the dynamics of UpdateKinematics or the contact space of CalcContactConstraint):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -12,7 +12,8 @@ enum Arith { kDouble = 0, kFloat = 1 };
 // link poses / velocities / Jacobians on their own (dwbc_link_query.h), gravity compensation alone or before such a redistribution
 // (dwbc_redistribute.h, GRAV = true)
 // the dynamics half of UpdateKinematics on its own (dwbc_dynamics.h)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6 };
+// SetContact + CalcContactConstraint on their own (dwbc_contact_space.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6, kContactSpace = 7 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -71,6 +72,10 @@ struct Request {
     // not a cycle either: the dynamics half of UpdateKinematics on its own (dwbc_batch_update_dynamics); of the members above it reads the
     // model and arith
     bool dynamics = false;
+    // not a cycle either: SetContact + CalcContactConstraint on their own (dwbc_batch_calc_contact_constraint); of the members above it reads
+    // the model, arith, max_active and n_contacts
+    bool contact_space = false;
+    int n_contacts = 0;  // registered contacts of the batch (read by the contact-space request alone)
 };
 
 struct Plan {
@@ -155,6 +160,15 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         const Row *r = Candidates(q, kRedist, tabs, n_tabs).pick(0u, 0u);
         if (!r) return refuse("no redistribution kernel for this model (built in for TOCABI's size and tree; kernel packs do not carry one)");
         if (!q.hqp) return refuse("redistribution of a supplied torque: hqp = true only (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque)");
+        return run(r, false);
+    }
+    // contact space of CalcContactConstraint: one kernel per model size and tree, whatever the batch size, the levels or the cycle's options are
+    if (q.contact_space) {
+        if (q.arith == kFloat) return refuse("contact space: fp64 batches only");
+        if (q.max_active > 2) return refuse("contact space: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
+        const Row *r = Candidates(q, kContactSpace, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no contact-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (q.n_contacts < 1) return refuse("contact space: no contact constraint (call dwbc_batch_add_contact first)");
         return run(r, false);
     }
     // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the

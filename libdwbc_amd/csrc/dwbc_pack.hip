@@ -3,7 +3,7 @@
 // (`make pack N=.. NB=..`; libdwbc_amd.build_pack(model) from Python).  The reference is model-generic (any URDF RBDL reads:
 // src/dwbc.cpp:140-277, tests/dof_test/*.urdf); here the kernels keep their matrices in registers, so the sizes are template
 // arguments and each (N, NB) is compiled once.  TopoGeneric build (dense A^-1 sweep), fp64, full-model cycle, the redistribution
-// of a caller-supplied torque, gravity compensation and the dynamics of UpdateKinematics; the reduced (centroidal) path is laid out for TOCABI's tree and is not part of a pack.  dwbc_batch_create() dlopens the pack of the
+// of a caller-supplied torque, gravity compensation, the dynamics of UpdateKinematics and the contact space of CalcContactConstraint; the reduced (centroidal) path is laid out for TOCABI's tree and is not part of a pack.  dwbc_batch_create() dlopens the pack of the
 // loaded model's size from the directory of libdwbc_hip.so (or $DWBC_PACK_DIR).
 #ifndef DWBC_PACK_N
 #error "compile with -DDWBC_PACK_N=<system dof> -DDWBC_PACK_NB=<bodies>"
@@ -45,6 +45,8 @@ static const dwbc_plan::Row kPack[] = {
     DWBC_ROW_GRAVCOMP(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
 // the dynamics half of UpdateKinematics on its own (dwbc_dynamics.h)
     DWBC_ROW_DYNAMICS(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
+// SetContact + CalcContactConstraint on their own (dwbc_contact_space.h)
+    DWBC_ROW_CONTACT_SPACE(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
 };
 
 #ifdef DWBC_PACK_PARENTS
