@@ -326,6 +326,7 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     constexpr bool kTree = !std::is_same<Topo, TopoGeneric>::value;
     static_assert(kTree, "the paired kernel is built for a constant kinematic tree");
     static_assert(kMaxActiveContacts == 2, "two 6D contacts");
+    static_assert(N + 1 <= 64 && NB <= 64 && NT >= 1, "one q entry and one body per lane (request phase, *_lane forms of dwbc_front.h)");
     DWBC_LANE_DECL;
     const bool is_main = wave <= 0, is_help = wave != 0;
     const int nb = NB;
@@ -334,16 +335,57 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     int *diag = io.diag ? io.diag + (size_t)inst * DG_COUNT : nullptr;
     DWBC_STAMP_INIT();
-    // ---- contact flags: both waves (uniform loads)
-    const unsigned char *fl = io.flags + (size_t)inst * su.n_contacts;
-    int act_c[kMaxActiveContacts] = {0, 0};
-    int nc = 0, nflag = 0;
-    for (int i = 0; i < su.n_contacts; i++) {
-        if (fl[i] && nc < kMaxActiveContacts) act_c[nc++] = i;
-        nflag += fl[i] ? 1 : 0;
+    // ---- request phase: whatever a wave takes from global memory in phases 0 - 1a is asked for here, before anything waits for a
+    // load, so that the trips overlap instead of following one another (profiles/pair_front_timeline.txt).  Loads come back in the
+    // order they were asked for, so what is used first is asked for first.  Main wave: q (the entry the lane copies to S::q, the
+    // joint angle of its body, the base pose), the kinematic part of the lane's body record, its parent and the CRBA pair words.
+    // Helper wave: f*.  Then both waves: the contact flags of the instance and the inertial part of the record with the length of
+    // the lane's subtree, which nothing reads before B0.  (The requests of one role first: a wait behind the two branches counts
+    // only the loads issued behind them, which are the same on both paths.)
+    const int npair = topo[3 * nb];
+    PLA(real_t, b_rec, kBodyStride);
+    PL(int, b_par);
+    PL(int, b_len);
+    real_t q_base[7] = {0, 0, 0, 0, 0, 0, 0};  // q[0..5], q[N]: the base pose
+    PL(real_t, q_cp);                          // q[lane]: the copy for S::q
+    PL(real_t, q_jt);                          // the joint angle of body `lane`
+    LANES { LV(q_cp) = real_t(0.0); LV(q_jt) = real_t(0.0); LV(b_par) = 0; }
+    int pairw[kCrbaPairRounds<N, NT>];
+    if (is_main) {
+        LANES {
+            LV(q_cp) = (real_t)qin[lane < N + 1 ? lane : 0];
+            LV(q_jt) = (real_t)qin[(lane >= 1 && lane < NB) ? 5 + lane : 0];
+        }
+        for (int a = 0; a < 6; a++) q_base[a] = (real_t)qin[a];
+        q_base[6] = (real_t)qin[N];
+        lane_record_fetch<NB, BF_RT, BF_MASS>(body, b_rec);
+        LANES { LV(b_par) = topo[lane < NB ? lane : 0]; }
+        // (crba_pairs_fetch without its branches: a word beyond the count repeats the last pair and is not used)
+#pragma unroll
+        for (int r = 0; r < kCrbaPairRounds<N, NT>; r++) pairw[r] = topo[3 * nb + 1 + (r * NT + th.tid < npair ? r * NT + th.tid : npair - 1)];
     }
-    const bool too_many = nflag > kMaxActiveContacts;
-    const int cd = 6 * nc, k = cd > 6 ? cd - 6 : 0;
+    static_assert(kMaxLevels * kMaxTaskDof <= 64, "one f* entry per lane");
+    PL(real_t, fs_req);
+    LANES { LV(fs_req) = real_t(0.0); }
+    if (is_help) {
+        const io_t *fin = io.fstar + (size_t)inst * su.fstar_total;
+        LANES {
+            if (lane < su.fstar_total) LV(fs_req) = (real_t)fin[lane];
+        }
+    }
+    // Contact flags: one byte load per declared contact, none beyond su.n_contacts -- nothing outside the instance's own flags is
+    // read.  A slot beyond the declared contacts reads a byte of the topo table instead (its value is not used): selecting the
+    // address keeps the loads free of branches, and a branch would have each flag waited for where it is loaded.  The bytes stay
+    // per-lane values until the scan below: a load the compiler knows to be uniform is read into a scalar register where it is
+    // issued, which waits for it there.
+    const unsigned char *fl = io.flags + (size_t)inst * su.n_contacts;
+    int flb[kMaxContacts];
+    int lane_zero = 0;
+    DWBC_FLAG_VGPR(lane_zero);
+#pragma unroll
+    for (int i = 0; i < kMaxContacts; i++) flb[i] = (i < su.n_contacts ? fl + i : (const unsigned char *)topo)[lane_zero];
+    lane_record_fetch<NB, BF_MASS, kBodyStride>(body, b_rec);
+    LANES { LV(b_len) = topo[2 * NB + (lane < NB ? lane : 0)]; }
     real_t *JCt = L + S::c_JC, *Yt = L + S::c_Y, *Lam = L + S::c_Lam, *JbT = L + S::JbT, *Vb = L + S::c_Vb, *VG = L + S::c_VG;
     real_t *flg = L + S::flg;  // [0] helper's contact status, [1] fast-route mask of the levels, [2] (free)
 
@@ -352,30 +394,49 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     int st_contact = 1;
 
     // ================= phase 0: kinematics up to the world transforms (main) =================
-    if (is_main) {
-        for (int i = th.tid; i < N + 1; i += NT) L[S::q + i] = (real_t)qin[i];
-        for (int i = th.tid; i < 3 * M; i += NT) L[S::tg + i] = real_t(0.0);
-        DWBC_SYNC();
-    }
-    const int npair = topo[3 * nb];
-    int pairw[kCrbaPairRounds<N, NT>];
-    if (is_main) crba_pairs_fetch<N, NT>(th, topo, nb, npair, pairw);
     real_t *Rw = L + S::Rw, *pw = L + S::pw, *aw = L + S::aw, *Rl = L + S::k_Rl;
     real_t *Iw = L + S::k_Iw, *Icm = L + S::k_Ic, *Sm = L + S::k_S, *Fm = L + S::k_F;
     if (is_main) {
-        joint_transforms<N, NT>(th, L + S::q, body, nb, Rw, pw, Rl);
-        // (second transform buffer: k_Rl and k_Iw; the ancestor table rides in k_Ic)
+        // (no fence behind these stores: the joint transforms take q from registers, and the first jump round begins with one)
+        LANES {
+            if (lane < N + 1) L[S::q + lane] = LV(q_cp);
+        }
+        for (int i = th.tid; i < 3 * M; i += NT) L[S::tg + i] = real_t(0.0);
+        DWBC_PSTAMP_M(56);  // q in LDS
+        // the local transforms go straight into the buffer the first jump round reads (second transform buffer: k_Rl and k_Iw; the
+        // ancestor table rides in k_Ic); between the rounds a lane keeps its own transform and ancestor in registers
         constexpr int kRounds = jump_rounds(Topo::maxdepth);
-        world_transforms_jump<NB, NT>(th, body, topo, nb, kRounds, Rw, pw, Rl, Iw, L + S::k_anc);
-        DWBC_SYNC();
-        world_axes<NT>(th, body, nb, Rw, aw);  // (the point Jacobians of the helper need them: before the barrier)
+        PLA(real_t, Ri, 9);
+        PLA(real_t, pi, 3);
+        PL(real_t, an);
+        joint_transforms_lane<NB>(q_base, q_jt, b_rec, b_par, kRounds, Rw, pw, Rl, Iw, L + S::k_anc, Ri, pi, an);
+        DWBC_PSTAMP_M(57);  // joint transforms
+        world_transforms_jump_lane<NB>(kRounds, Rw, pw, Rl, Iw, L + S::k_anc, Ri, pi, an);
+        DWBC_PSTAMP_M(58);  // last jump round
+        world_axes_lane<NB>(b_rec, Ri, aw);  // (the point Jacobians of the helper need them: before the barrier)
+        DWBC_PSTAMP_M(59);  // world axes
     }
     if (is_help) {
         // f* of every level (the lean build has no on-device task reference: the SetTaskSpace values)
-        const io_t *fin = io.fstar + (size_t)inst * su.fstar_total;
-        for (int i = th.tid; i < su.fstar_total; i += NT) L[S::fs + i] = (real_t)fin[i];
+        LANES {
+            if (lane < su.fstar_total) L[S::fs + lane] = LV(fs_req);
+        }
         if (th.tid == 0) { flg[0] = real_t(1.0); flg[1] = real_t(0.0); }
     }
+    // ---- contact flags: both waves.  Scanned here, where the loads of the request phase are long back: nothing before B0 uses them.
+    int act_c[kMaxActiveContacts] = {0, 0};
+    int nc = 0, nflag = 0;
+#pragma unroll
+    for (int i = 0; i < kMaxContacts; i++) {
+        if (i < su.n_contacts) {
+            const int f_ = DWBC_FLAG_UNIFORM(flb[i]);
+            if (f_ && nc < kMaxActiveContacts) act_c[nc++] = i;
+            nflag += f_ ? 1 : 0;
+        }
+    }
+    if (is_main) DWBC_PSTAMP_M(55);  // contact flags scanned (main wave: both waves have a lane 0)
+    const bool too_many = nflag > kMaxActiveContacts;
+    const int cd = 6 * nc, k = cd > 6 ? cd - 6 : 0;
     DWBC_PAIR_BARRIER(0);  // ---- B0: Rw, pw, aw
 
     // ================= phase 1 =================
@@ -383,16 +444,16 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     // places -- and takes five of the ten components through the prefix scan; the halves meet at B0a).  The window sums of the one-wave
     // kernels (six rounds through LDS) were 7.3 k of this wave's 17 k cycles before the A^-1 sweep.
     if (is_main) {
-        world_inertias<NT, false>(th, body, nb, Rw, pw, Iw);
+        world_inertias_lane<NB>(b_rec, Rw, pw, Iw);
         DWBC_SYNC();
         DWBC_PSTAMP_M(51);  // world inertias
-        composite_inertias_scan<0, 5>(topo, nb, Iw, Icm);
+        composite_inertias_scan_lane<0, 5>(b_len, nb, Iw, Icm);
         DWBC_SYNC();
     }
     if (is_help) {
-        world_inertias<NT, false>(th, body, nb, Rw, pw, Iw);
+        world_inertias_lane<NB>(b_rec, Rw, pw, Iw);
         DWBC_SYNC();
-        composite_inertias_scan<5, 10>(topo, nb, Iw, Icm);
+        composite_inertias_scan_lane<5, 10>(b_len, nb, Iw, Icm);
         DWBC_SYNC();
     }
     if (is_main) {
@@ -454,6 +515,7 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
             }
             DWBC_SYNC();
         }
+        DWBC_PSTAMP_M(60);  // helper at B1a
     }
     DWBC_PAIR_BARRIER_X();  // ---- B1a: J_C, J_t, G in LDS; the columns of A in the main wave's registers
     real_t *AJt = L + S::ajt;

@@ -193,6 +193,193 @@ DWBC_DEV void composite_inertias_scan(const int *topo, int nb, const real_t *Iw,
     }
 }
 
+// ---- Forms of the two-wave kernel (dwbc_cycle2p.h), where a wave has one body per lane (64 >= nb): the lane's record of the body
+// table and its topo words are requested at the top of the kernel (lane_record_fetch and the topo words beside it) and taken from registers here, so that no
+// routine of the front end waits out a trip to global memory of its own.  The expressions are those of the forms above, in the same
+// order.  Lanes >= nb hold the record of body 0 and store nothing.  The forms above are left as they are: the general-contact
+// kernel calls them.
+
+// fields [F0, F1) of the lane's record: loads only, no wait
+template <int NB, int F0, int F1>
+DWBC_DEV void lane_record_fetch(const real_t *body, PLA_REF(real_t, rec, kBodyStride)) {
+    DWBC_LANE_DECL;
+    LANES {
+        const int bi = lane < NB ? lane : 0;
+#pragma unroll
+        for (int a = F0; a < F1; a++) LV(rec)[a] = body[bi * kBodyStride + a];
+    }
+}
+
+// joint_transforms and the start of world_transforms_jump in one: the lane's local transform (body 0: the base pose), its constant
+// offset p_T and its parent as the first ancestor go straight into the buffer the first jump round reads, and stay in (Ri, pi, an).
+// qb: q[0..5] and q[N]; qj: the joint angle of the lane's body.
+template <int NB>
+DWBC_DEV void joint_transforms_lane(const real_t (&qb)[7], PL_REF(real_t, qj), PLA_REF(real_t, rec, kBodyStride), PL_REF(int, par), int rounds,
+                                    real_t *Rw, real_t *pw, real_t *Rl, real_t *p_alt, real_t *anc, PLA_REF(real_t, Ri, 9),
+                                    PLA_REF(real_t, pi, 3), PL_REF(real_t, an)) {
+    const bool odd = rounds & 1;
+    real_t *Rc = odd ? Rl : Rw, *pc = odd ? p_alt : pw;
+    DWBC_LANE_DECL;
+    LANES {
+        const int i = lane;
+        const real_t *bd = LV(rec);
+        if (i == 0) {
+            const real_t x = qb[3], y = qb[4], z = qb[5], w = qb[6];
+            real_t *R = LV(Ri);
+#if defined(DWBC_HOST_EMU)
+            R[0] = 1 - 2 * y * y - 2 * z * z; R[1] = 2 * x * y - 2 * w * z; R[2] = 2 * x * z + 2 * w * y;
+            R[3] = 2 * x * y + 2 * w * z; R[4] = 1 - 2 * x * x - 2 * z * z; R[5] = 2 * y * z - 2 * w * x;
+            R[6] = 2 * x * z - 2 * w * y; R[7] = 2 * y * z + 2 * w * x; R[8] = 1 - 2 * x * x - 2 * y * y;
+#else
+            // The same nine expressions with the fused multiply-adds written out as the compiler forms them in joint_transforms: each
+            // entry is a sum of two products of which either may be the fused one, and left to itself the compiler fuses the other one
+            // here (its choice follows the order it meets the stores in), which moves a tilted base rotation in the last bit.
+            const auto fm = [](real_t a, real_t b, real_t c) {
+                if constexpr (sizeof(real_t) == 8) return (real_t)__builtin_fma(a, b, c);
+                else return (real_t)__builtin_fmaf(a, b, c);
+            };
+            const real_t x2 = x + x, y2 = y + y, z2 = z + z, w2 = w + w;
+            const real_t zw = z * w2, yw = y * w2, xw = x * w2;
+            const real_t oy = fm(-y, y2, real_t(1.0)), ox = fm(-x, x2, real_t(1.0));
+            R[0] = fm(-z, z2, oy); R[1] = fm(x2, y, -zw); R[2] = fm(x2, z, yw);
+            R[3] = fm(x2, y, zw); R[4] = fm(-z, z2, ox); R[5] = fm(y2, z, -xw);
+            R[6] = fm(x2, z, -yw); R[7] = fm(y2, z, xw); R[8] = fm(-y, y2, ox);
+#endif
+            LV(pi)[0] = qb[0]; LV(pi)[1] = qb[1]; LV(pi)[2] = qb[2];
+            LV(an) = -real_t(1.0);
+        } else {
+            const real_t ax = bd[BF_AXIS], ay = bd[BF_AXIS + 1], az = bd[BF_AXIS + 2];
+            real_t sn, cs;
+            sincos_r(LV(qj), &sn, &cs);
+            const real_t c1 = real_t(1.0) - cs;
+            real_t Rj[9];
+            Rj[0] = cs + ax * ax * c1; Rj[1] = ax * ay * c1 - az * sn; Rj[2] = ax * az * c1 + ay * sn;
+            Rj[3] = ay * ax * c1 + az * sn; Rj[4] = cs + ay * ay * c1; Rj[5] = ay * az * c1 - ax * sn;
+            Rj[6] = az * ax * c1 - ay * sn; Rj[7] = az * ay * c1 + ax * sn; Rj[8] = cs + az * az * c1;
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++)
+                    LV(Ri)[a * 3 + b] = bd[BF_RT + a * 3] * Rj[b] + bd[BF_RT + a * 3 + 1] * Rj[3 + b] + bd[BF_RT + a * 3 + 2] * Rj[6 + b];
+            for (int a = 0; a < 3; a++) LV(pi)[a] = bd[BF_PT + a];
+            LV(an) = (real_t)LV(par);
+        }
+        if (i < NB) {
+            for (int a = 0; a < 9; a++) Rc[i * 9 + a] = LV(Ri)[a];
+            for (int a = 0; a < 3; a++) pc[i * 3 + a] = LV(pi)[a];
+            anc[i] = LV(an);
+        }
+    }
+}
+
+// the rounds of world_transforms_jump on the buffers joint_transforms_lane filled: a lane keeps its own transform and ancestor in
+// registers and reads the ancestor's only.  A DWBC_SYNC() before every round; on return (Ri, pi) is the lane's world transform, as
+// stored in (Rw, pw).
+template <int NB>
+DWBC_DEV void world_transforms_jump_lane(int rounds, real_t *Rw, real_t *pw, real_t *Rl, real_t *p_alt, real_t *anc, PLA_REF(real_t, Ri, 9),
+                                         PLA_REF(real_t, pi, 3), PL_REF(real_t, an)) {
+    const bool odd = rounds & 1;  // start in the buffer that makes the last round land in (Rw, pw)
+    real_t *Rc = odd ? Rl : Rw, *Rn = odd ? Rw : Rl;
+    real_t *pc = odd ? p_alt : pw, *pn = odd ? pw : p_alt;
+    real_t *ac = anc, *an_ = anc + NB;
+    DWBC_LANE_DECL;
+    for (int r = 0; r < rounds; r++) {
+        DWBC_SYNC();
+        LANES {
+            const int i = lane;
+            if (i < NB) {
+                const int ai = (int)LV(an);
+                const int aa = ai < 0 ? 0 : ai;
+                real_t Ra[9], pa[3];
+                for (int a = 0; a < 9; a++) Ra[a] = Rc[aa * 9 + a];
+                for (int a = 0; a < 3; a++) pa[a] = pc[aa * 3 + a];
+                const real_t a2 = ac[aa];
+                real_t Ro[9], po[3];
+                for (int a = 0; a < 3; a++) {
+                    for (int c = 0; c < 3; c++)
+                        Ro[a * 3 + c] = Ra[a * 3] * LV(Ri)[c] + Ra[a * 3 + 1] * LV(Ri)[3 + c] + Ra[a * 3 + 2] * LV(Ri)[6 + c];
+                    po[a] = pa[a] + Ra[a * 3] * LV(pi)[0] + Ra[a * 3 + 1] * LV(pi)[1] + Ra[a * 3 + 2] * LV(pi)[2];
+                }
+                for (int a = 0; a < 9; a++) LV(Ri)[a] = ai < 0 ? LV(Ri)[a] : Ro[a];
+                for (int a = 0; a < 3; a++) LV(pi)[a] = ai < 0 ? LV(pi)[a] : po[a];
+                LV(an) = ai < 0 ? -real_t(1.0) : a2;
+                for (int a = 0; a < 9; a++) Rn[i * 9 + a] = LV(Ri)[a];
+                for (int a = 0; a < 3; a++) pn[i * 3 + a] = LV(pi)[a];
+                an_[i] = LV(an);
+            }
+        }
+        { real_t *t_ = Rc; Rc = Rn; Rn = t_; t_ = pc; pc = pn; pn = t_; t_ = ac; ac = an_; an_ = t_; }
+    }
+}
+
+// world joint axes from the lane's world rotation in registers
+template <int NB>
+DWBC_DEV void world_axes_lane(PLA_REF(real_t, rec, kBodyStride), PLA_REF(real_t, Ri, 9), real_t *aw) {
+    DWBC_LANE_DECL;
+    LANES {
+        if (lane < NB) world_axis(LV(rec), LV(Ri), aw, lane);
+    }
+}
+
+// world_inertias<NT, false> with the lane's mass, COM and inertia from its record
+template <int NB>
+DWBC_DEV void world_inertias_lane(PLA_REF(real_t, rec, kBodyStride), const real_t *Rw, const real_t *pw, real_t *Iw) {
+    DWBC_LANE_DECL;
+    LANES {
+        const int i = lane;
+        if (i < NB) {
+            const real_t *bd = LV(rec);
+            const real_t *R = Rw + i * 9;
+            const real_t m = bd[BF_MASS];
+            real_t r[3];
+            for (int a = 0; a < 3; a++)
+                r[a] = pw[i * 3 + a] + R[a * 3] * bd[BF_COM] + R[a * 3 + 1] * bd[BF_COM + 1] + R[a * 3 + 2] * bd[BF_COM + 2] - pw[a];
+            const real_t Ic[9] = {bd[BF_ICOM], bd[BF_ICOM + 1], bd[BF_ICOM + 2], bd[BF_ICOM + 1], bd[BF_ICOM + 3],
+                                  bd[BF_ICOM + 4], bd[BF_ICOM + 2], bd[BF_ICOM + 4], bd[BF_ICOM + 5]};
+            real_t Tm[9];
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++) Tm[a * 3 + b] = R[a * 3] * Ic[b] + R[a * 3 + 1] * Ic[3 + b] + R[a * 3 + 2] * Ic[6 + b];
+            const real_t rr2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+            real_t *o = Iw + i * 10;
+            o[0] = m;
+            o[1] = m * r[0]; o[2] = m * r[1]; o[3] = m * r[2];
+            int c = 4;
+            for (int a = 0; a < 3; a++)
+                for (int b = a; b < 3; b++) {
+                    real_t v = Tm[a * 3] * R[b * 3] + Tm[a * 3 + 1] * R[b * 3 + 1] + Tm[a * 3 + 2] * R[b * 3 + 2];
+                    v += m * ((a == b ? rr2 : real_t(0.0)) - r[a] * r[b]);
+                    o[c++] = v;
+                }
+        }
+    }
+}
+
+// composite_inertias_scan with the length of the lane's subtree from its register
+template <int C0, int C1>
+DWBC_DEV void composite_inertias_scan_lane(PL_REF(int, len), int nb, const real_t *Iw, real_t *Icm) {
+    constexpr int NCP = C1 - C0;
+    DWBC_LANE_DECL;
+    PLA(real_t, pf, NCP);
+    LANES {
+        const int bi = lane < nb ? lane : 0;
+#pragma unroll
+        for (int c = 0; c < NCP; c++) {
+            const real_t v_ = Iw[bi * 10 + C0 + c];
+            LV(pf)[c] = lane < nb ? v_ : real_t(0.0);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NCP; c++) WAVE_PREFIX_A(pf, c);
+    LANES {
+        int e_ = lane + (lane < nb ? LV(len) : 1) - 1;
+        e_ = e_ < 63 ? e_ : 63;
+        const int s_ = lane > 0 ? lane - 1 : 0;
+#pragma unroll
+        for (int c = 0; c < NCP; c++) {
+            const real_t hi_ = SHFLA(pf, c, e_), lo_ = SHFLA(pf, c, s_);
+            if (lane < nb) Icm[lane * 10 + C0 + c] = hi_ - (lane > 0 ? lo_ : real_t(0.0));
+        }
+    }
+}
+
 // motion axes S_j = [omega; v_O] about O = pelvis origin (N x 6): base translations, base rotations, then joint j on body j - 5
 template <int N, int NT>
 DWBC_DEV void motion_axes(Thr th, const real_t *Rw, const real_t *pw, const real_t *aw, real_t *Sm) {

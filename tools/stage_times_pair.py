@@ -40,13 +40,20 @@ for i, n in ((5, "stage 3a (J_kt, X, null-space chain)"), (6, "wrench maps (MFMA
     if t[i] > 0:
         print(f"{n:44s} {t[i] - prev:10.0f} {t[i]:12.0f}")
         prev = t[i]
-fine = {51: "phase 1: world inertias", 52: "phase 1: composite inertias (both waves), S", 53: "phase 1: F", 54: "phase 1: mass-matrix pairs staged", 41: "phase 1: CRBA done (A^-1 sweep starts)", 42: "phase 2: Y = J_C A^-1 stored", 43: "phase 2: Lambda_c", 45: "phase 4: D Lambda_c of every slot, P_C", 46: "phase 4: cv (base residuals)", 47: "phase 4: E = Lambda_c d - lam", 48: "phase 4: tau_any", 49: "phase 4: (I - P) tau_any",
+fine = {55: "phase 0: contact flags scanned", 56: "phase 0: q in LDS", 57: "phase 0: joint transforms", 58: "phase 0: last jump round", 59: "phase 0: world axes",
+        60: "phase 1a: HELPER wave at B1a (its own clock reading)", 51: "phase 1: world inertias", 52: "phase 1: composite inertias (both waves), S", 53: "phase 1: F", 54: "phase 1: mass-matrix pairs staged", 41: "phase 1: CRBA done (A^-1 sweep starts)", 42: "phase 2: Y = J_C A^-1 stored", 43: "phase 2: Lambda_c", 45: "phase 4: D Lambda_c of every slot, P_C", 46: "phase 4: cv (base residuals)", 47: "phase 4: E = Lambda_c d - lam", 48: "phase 4: tau_any", 49: "phase 4: (I - P) tau_any",
         16: "level-0 J_kt / X rows in registers", 17: "level-0 chain done", 18: "level-1 J_kt / X rows in registers", 19: "level-1 chain done", 24: "level-0 QP: rows ready", 25: "level-0 QP: committed",
         26: "redistribution QP: rows ready", 27: "redistribution QP: committed", 28: "torques stored"}
-print("fine stamps of the main wave (cumulative):")
+print("fine stamps of the main wave (cumulative; stamp 60 is the helper wave's):")
 for i in sorted(fine, key=lambda i_: f[i_]):
     if f[i] > 0:
         print(f"  {fine[i]:44s} {f[i]:12.0f}")
+# ---- the front end: the launch ends with its slowest instance, so the spread over the batch beside the median
+print("front end over the batch (main wave):  median / 99th percentile / slowest instance")
+for n, v in (("B0 link frames", d[:, 74 + 0]), ("CRBA done (stamp 41)", d[:, 90 + 41]), ("B1 A^-1", d[:, 74 + 1]), ("total", d[:, 74 + 15])):
+    v = v.astype(np.float64)
+    if v.max() > 0:
+        print(f"  {n:24s} {np.median(v):10.0f} {np.percentile(v, 99):10.0f} {v.max():10.0f}")
 qn = ["post-loop", "slack + arg-min", "publish n, r, z", "step / drop", "commit", "lexicographic point (CG)", "normalise rows, init", "feasibility of the point", "row fill"]
 print("level-0 QP solver sections (cycles, summed over iterations):")
 for i, n in enumerate(qn):
