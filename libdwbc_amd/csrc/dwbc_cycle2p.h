@@ -262,10 +262,31 @@ DWBC_WDEV void wave_gemm(FA fa, FB fb, FS fstore) {
     wave_gemm<MR, NCV, KV, SYNC_STORE>(fa, fb, fstore, [](int, int) { return real_t(0.0); });
 }
 
+// One pivot of the 12-wide sweep with the pivot column taken by row broadcast (dwbc_wave.h): lane i < 12 holds column i, the matrix
+// stays symmetric, so the entry row update i needs is s[K] of lane i -- row_newbcast:i on a copy of s[K] (s[K] itself is updated
+// at i = K).  Same arithmetic per row update as lds_pivot<12, K> (dwbc_cycle2.h), whose LDS buffer held exactly these copies:
+// s[i] -= col[i] * h as ONE fma, here fma(col[i], -h, s[i]).  Lanes 12..63 hold zero columns (h = 0): rows 1 - 3 are inert.
+#if !defined(DWBC_HOST_EMU)
+template <int K>
+__device__ __forceinline__ void rowbc_pivot12(double (&s)[12], double &dg2, int &ok, int lane) {
+    double d = readlane_f64(dg2, K) + 2.0;
+    int pos = d > 0.0 ? 1 : 0;
+    DWBC_FLAG_VGPR(pos);
+    ok &= pos;
+    if (!(d > 0.0)) d = 1.0;
+    const double rp = fast_rcp(d);
+    const double cj = s[K];     // pivot lane: d - 1
+    const double h = cj * rp;   // pivot lane: 1 - 1/d, the multiplier of the pivot column itself
+    rowbc_axpy<12>(s, cj, -h);
+    dg2 = (lane == K) ? -rp : dg2 - cj * h;  // (pivot lane: -1/d from rp, see lds_pivot)
+    if constexpr (K > 0) rowbc_pivot12<K - 1>(s, dg2, ok, lane);
+}
+#endif
+
 // Lambda_c^-1 -> Lambda_c for two active contacts, IN PLACE (M: 12 x 12, dense): spd_inverse_small's Jacobi-scaled symmetric sweep
-// (dwbc_cycle2.h: same scaling, same pivots, same arithmetic per row update) with the pivot column fed through LDS instead of
-// v_readlane -- per pivot one ds_write_b64 and six broadcast ds_read_b128 against 24 v_readlane + 12 s_nop.  The matrix sits in
-// registers during the sweep, so its own LDS block serves as the column buffer; scl: 12 doubles for the scale factors.
+// (dwbc_cycle2.h: same scaling, same pivots, same arithmetic per row update) with the pivot column broadcast inside DPP row 0 by the
+// FMA itself (rowbc_pivot12) -- per pivot 12 v_fmac_f64_dpp and nothing else, against one ds_write_b64, six ds_read_b128 and their
+// round trip (the LDS-fed form this replaces), or 24 v_readlane + 12 s_nop.  scl: 12 doubles for the scale factors.
 template <class R>
 DWBC_WDEV int spd_inverse12_lds(R *Mx, R *Out, R *scl) {
 #if defined(DWBC_HOST_EMU)
@@ -294,7 +315,7 @@ DWBC_WDEV int spd_inverse12_lds(R *Mx, R *Out, R *scl) {
         const double d_ = Mx[col * 12 + col] * dsc * dsc;
         dg = lane < 12 ? d_ : 1.0;
     }
-    DWBC_SYNC();  // (the matrix is in registers: its block is the column buffer now)
+    DWBC_SYNC();  // (the matrix is in registers)
     int ok = 1;
     {
         DWBC_LANE_OPAQUE(lp);
@@ -302,7 +323,7 @@ DWBC_WDEV int spd_inverse12_lds(R *Mx, R *Out, R *scl) {
         for (int i = 0; i < 12; i++) s[i] = (i == lp) ? dg - 1.0 : s[i];
     }
     double dg2 = dg - 2.0;
-    lds_pivot<12, 11, 0>(s, dg2, ok, (unsigned)(size_t)Mx, lane);
+    rowbc_pivot12<11>(s, dg2, ok, lane);
     ok = DWBC_FLAG_UNIFORM(ok);
     DWBC_SYNC();
     if (lane < 12) {

@@ -11,7 +11,7 @@
 // the step length anyway).  The Goldfarb-Idnani operators live in one 12-register array per lane: lanes 0..11 hold the
 // rows of H = I - N N^+ (projector on the null space of the active normals), lanes 16..27 the rows of N^+, one working-
 // set slot each.  So z = H n and r = N^+ n are a single 12-FMA dot product per lane against the normal broadcast with
-// v_readlane, adding a constraint is one rank-one update M -= coef * z^T shared by both operators, and dropping one is
+// v_readlane (z itself, the operand of the products that follow: by row broadcast inside the FMA, see kRowBc), adding a constraint is one rank-one update M -= coef * z^T shared by both operators, and dropping one is
 // the inverse rank-one update -- no refactorisation, no LDS round trip, no triangular solve in the loop.
 // The final point (DESIGN.md "QP canon") comes from a column-pivoted Householder QR of the weighted working-set
 // normals done in place in the owner lanes (no gather), fully unrolled over the elimination step.
@@ -86,6 +86,11 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
     static_assert(NV <= QN && NV <= 24, "variable count");
     constexpr int SB = NV > 16 ? 32 : 16;  // first working-set slot lane (the H rows take lanes 0..NV-1)
     const int k = nv - t;
+    // z = H n, produced one entry per lane in lanes 0..NV-1, is the uniform operand of dz = R.g . z, of the re-projection and of the
+    // rank-one update on add.  fp64 and NV <= 16 (z inside one DPP row): replicated to rows 1 - 3 once behind the first product, it is
+    // broadcast by the FMA itself (ROWBC_*, dwbc_wave.h).  The fp32 build and the 18- and 24-variable instantiations (z spans two rows)
+    // read it out with v_readlane into zu[].  Same operations in the same order either way.
+    constexpr bool kRowBc = !kF32 && NV <= 16;
     PLA(real_t, Mx, NV);  // lanes 0..11: row of H;  lanes 16..27: row of N^+ for working-set slot lane-16
     PL(real_t, d);          // g . x of the own row (normalised row, scaled variables)
     PL(real_t, fs);         // |g| / |a|: factor from the normalised slack to slack / (norm of the unscaled row)
@@ -209,13 +214,20 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
             LV(m) = sgn * s_;  // lanes 0..11: z = H n;  slot lanes: r = N^+ n
         }
         real_t zu[NV];
+        PL(real_t, mz);  // (row-broadcast route) z in lanes 0..NV-1 of EVERY DPP row; m keeps r = N^+ n in the slot lanes
+        if constexpr (kRowBc) {
+            LANES { LV(mz) = LV(m); LV(dz) = real_t(0.0); }
+            ROW_REPLICATE(mz);
+            ROWBC_DOT(NV, dz, mz, R.g);  // change of g.x per unit step along z
+        } else {
 #pragma unroll
-        for (int i = 0; i < NV; i++) zu[i] = BCAST(m, i);
-        LANES {
-            real_t s_ = real_t(0.0);
+            for (int i = 0; i < NV; i++) zu[i] = BCAST(m, i);
+            LANES {
+                real_t s_ = real_t(0.0);
 #pragma unroll
-            for (int j = 0; j < NV; j++) s_ += LV(R.g)[j] * zu[j];
-            LV(dz) = s_;  // change of g.x per unit step along z
+                for (int j = 0; j < NV; j++) s_ += LV(R.g)[j] * zu[j];
+                LV(dz) = s_;  // change of g.x per unit step along z
+            }
         }
         real_t zg = sgn * BCAST(dz, p);  // n.z = |z|^2
         // z = H n loses digits when n lies close to the span of the working set (the rows are unit vectors, so |z|^2 is the squared
@@ -223,19 +235,32 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
         // Without it the final point carries ~1e-9 relative round-off on tilted feet (3e-7 Nm against the oracle instead of 2e-8);
         // about one step in five takes this branch.
         if (zg < kQpReorth) {
-            LANES {
-                real_t s_ = real_t(0.0);
+            if constexpr (kRowBc) {
+                PL(real_t, hz);
+                LANES { LV(hz) = real_t(0.0); }
+                ROWBC_DOT(NV, hz, mz, Mx);
+                LANES {
+                    if (lane < NV) LV(m) = LV(hz);  // (the slot lanes keep r = N^+ n)
+                    LV(mz) = LV(m);
+                    LV(dz) = real_t(0.0);
+                }
+                ROW_REPLICATE(mz);
+                ROWBC_DOT(NV, dz, mz, R.g);
+            } else {
+                LANES {
+                    real_t s_ = real_t(0.0);
 #pragma unroll
-                for (int j = 0; j < NV; j++) s_ += LV(Mx)[j] * zu[j];
-                if (lane < NV) LV(m) = s_;  // (the slot lanes keep r = N^+ n)
-            }
+                    for (int j = 0; j < NV; j++) s_ += LV(Mx)[j] * zu[j];
+                    if (lane < NV) LV(m) = s_;  // (the slot lanes keep r = N^+ n)
+                }
 #pragma unroll
-            for (int i = 0; i < NV; i++) zu[i] = BCAST(m, i);
-            LANES {
-                real_t s_ = real_t(0.0);
+                for (int i = 0; i < NV; i++) zu[i] = BCAST(m, i);
+                LANES {
+                    real_t s_ = real_t(0.0);
 #pragma unroll
-                for (int j = 0; j < NV; j++) s_ += LV(R.g)[j] * zu[j];
-                LV(dz) = s_;
+                    for (int j = 0; j < NV; j++) s_ += LV(R.g)[j] * zu[j];
+                    LV(dz) = s_;
+                }
             }
             zg = sgn * BCAST(dz, p);
         }
@@ -276,14 +301,20 @@ DWBC_WDEV void qp_solve_wave(QpRowsT<QN> &R, int nv, int t, int max_iter, QpResu
             // working set += (p, side): H -= z z^T / zg, N^+ rows -= r_a z^T / zg, new N^+ row = z^T / zg
             const int slot = __builtin_ctz(~(unsigned)used);  // lowest free slot (q < nv <= NV: there is one)
             const real_t inv_ = fast_rcp(zg);
+            PL(real_t, ncoef);
             LANES {
                 real_t coef = LV(m) * inv_;
                 if (lane == SB + slot) { coef = -inv_; LV(u) = up; LV(akey) = kmin; }
+                if constexpr (kRowBc) {
+                    LV(ncoef) = -coef;  // Mx[j] -= coef * z[j] as fma(z[j], -coef, Mx[j]), behind this block
+                } else {
 #pragma unroll
-                for (int j = 0; j < NV; j++) LV(Mx)[j] -= coef * zu[j];
+                    for (int j = 0; j < NV; j++) LV(Mx)[j] -= coef * zu[j];
+                }
                 LV(ehi) = ((lane << 1) == kmin) ? DWBC_QP_INF : LV(ehi);  // (kmin = (p << 1) | side)
                 LV(elo) = (((lane << 1) | 1) == kmin) ? DWBC_QP_INF : LV(elo);
             }
+            if constexpr (kRowBc) ROWBC_AXPY(NV, Mx, mz, ncoef);
             used |= 1 << slot;
             q++;
             pick = true;

@@ -362,3 +362,105 @@ __device__ __forceinline__ unsigned long long argmin_key(real_t v, int lane) {
         out_k = dwbc::readlane_i32((key), wl_);                                                    \
     } while (0)
 #endif
+
+// ---- row-broadcast FMA and row replicate (fp64): a vector held one entry per lane inside ONE DPP row of 16 lanes as the uniform
+// operand of a product, without v_readlane and without LDS.  v_fma_f64 is VOP3 and has no DPP form; v_fmac_f64 is VOP2 and has one
+// (gfx90a and later) with the single 64-bit DPP control row_newbcast:J -- every lane takes src0 from lane J of its own row -- so the
+// broadcast and the FMA are one instruction (tools/ubench/ubench2.hip modes 16 - 20, profiles/rowbc_ubench.txt).
+//   ROWBC_FMA(J, acc, x, y)      acc    += x[(lane & ~15) | J] * y              one FMA, J a literal 0..15
+//   ROWBC_DOT(N, acc, x, y)      acc    += x[(lane & ~15) | j] * y[j]           j = 0 .. N-1 in this order, ONE accumulator (N = 6, 9, 12)
+//   ROWBC_AXPY(N, a, x, c)       a[j]   += x[(lane & ~15) | j] * c              j = 0 .. N-1 (N = 6, 9, 12)
+//   ROW_REPLICATE(x)             x of lanes 16..63 = x of lane (lane & 15)      (DPP row 0 copied to rows 1 - 3)
+// Device: every product is ONE fused multiply-add, the v_fma_f64 the compiler contracts `acc += a * b` to.  An accumulator started at
+// -0.0 makes the first term the plain product a * b (sign of a zero included), one started at +0.0 the fma(a, b, +0.0) of `0.0 + a * b`.
+// Host emulation: `acc += a * b` in the host compiler's arithmetic, like every other product of the emulation.
+// Preconditions (device): the source lane must be ACTIVE, so these are called only where the wave is convergent -- never inside
+// `if (lane < ...)`: mask the result instead.  The asm forms carry their own hazard pad: the DPP source must be two wait states away
+// from the VALU instruction that wrote it (`s_nop 1` opening the string, once per chain); a chain is ONE statement so that the compiler
+// cannot put a copy of the source between the pad and its reader; the accumulators are early-clobber operands, so none of them shares
+// a register with x, y or c even where the values are the same (the sweep's x IS one of its accumulators' old value).  The five wait states a DPP read needs behind a VALU write of EXEC
+// (v_cmpx) are not padded: the kernels that use these have no v_cmpx (profiles/rowbc_codeobj.txt).
+// Host emulation: whole-wave statements outside LANES blocks, like WAVE_*; legal by the rule at the top as long as x was written in an
+// earlier LANES block and is none of the accumulators.
+#ifdef DWBC_HOST_EMU
+#define ROWBC_FMA(J, acc, x, y)                                                                                        \
+    do {                                                                                                               \
+        for (int l_ = 0; l_ < 64; l_++) (acc)[l_] += (x)[(l_ & ~15) | (J)] * (y)[l_];          \
+    } while (0)
+#define ROWBC_DOT(N, acc, x, y)                                                                                        \
+    do {                                                                                                               \
+        for (int l_ = 0; l_ < 64; l_++)                                                                                \
+            for (int j_ = 0; j_ < (N); j_++) (acc)[l_] += (x)[(l_ & ~15) | j_] * (y)[l_][j_];  \
+    } while (0)
+#define ROWBC_AXPY(N, a, x, c)                                                                                         \
+    do {                                                                                                               \
+        for (int l_ = 0; l_ < 64; l_++)                                                                                \
+            for (int j_ = 0; j_ < (N); j_++) (a)[l_][j_] += (x)[(l_ & ~15) | j_] * (c)[l_];  \
+    } while (0)
+#define ROW_REPLICATE(x)                                                                                               \
+    do {                                                                                                               \
+        for (int l_ = 16; l_ < 64; l_++) (x)[l_] = (x)[l_ & 15];                                                       \
+    } while (0)
+#else
+namespace dwbc {
+#define DWBC_RB_DOT_(j, y) "v_fmac_f64_dpp %0, %1, %" #y " row_newbcast:" #j " row_mask:0xf bank_mask:0xf\n"
+#define DWBC_RB_AXPY_(j, x, c) "v_fmac_f64_dpp %" #j ", %" #x ", %" #c " row_newbcast:" #j " row_mask:0xf bank_mask:0xf\n"
+template <int J>
+__device__ __forceinline__ void rowbc_fma(double &acc, double x, double y) {
+    static_assert(J >= 0 && J < 16, "a lane of the own DPP row");
+    asm volatile("s_nop 1\nv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+&v"(acc) : "v"(x), "v"(y), "n"(J));
+}
+template <int N, int NY>
+__device__ __forceinline__ void rowbc_dot(double &acc, double x, const double (&y)[NY]) {
+    static_assert((N == 6 || N == 9 || N == 12) && N <= NY, "chain lengths of the wave QP");
+    if constexpr (N == 6)
+        asm volatile("s_nop 1\n" DWBC_RB_DOT_(0, 2) DWBC_RB_DOT_(1, 3) DWBC_RB_DOT_(2, 4) DWBC_RB_DOT_(3, 5) DWBC_RB_DOT_(4, 6) DWBC_RB_DOT_(5, 7)
+                     : "+&v"(acc) : "v"(x), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]));
+    if constexpr (N == 9)
+        asm volatile("s_nop 1\n" DWBC_RB_DOT_(0, 2) DWBC_RB_DOT_(1, 3) DWBC_RB_DOT_(2, 4) DWBC_RB_DOT_(3, 5) DWBC_RB_DOT_(4, 6) DWBC_RB_DOT_(5, 7)
+                     DWBC_RB_DOT_(6, 8) DWBC_RB_DOT_(7, 9) DWBC_RB_DOT_(8, 10)
+                     : "+&v"(acc) : "v"(x), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]), "v"(y[6]), "v"(y[7]), "v"(y[8]));
+    if constexpr (N == 12)
+        asm volatile("s_nop 1\n" DWBC_RB_DOT_(0, 2) DWBC_RB_DOT_(1, 3) DWBC_RB_DOT_(2, 4) DWBC_RB_DOT_(3, 5) DWBC_RB_DOT_(4, 6) DWBC_RB_DOT_(5, 7)
+                     DWBC_RB_DOT_(6, 8) DWBC_RB_DOT_(7, 9) DWBC_RB_DOT_(8, 10) DWBC_RB_DOT_(9, 11) DWBC_RB_DOT_(10, 12) DWBC_RB_DOT_(11, 13)
+                     : "+&v"(acc) : "v"(x), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]), "v"(y[6]), "v"(y[7]), "v"(y[8]), "v"(y[9]),
+                       "v"(y[10]), "v"(y[11]));
+}
+template <int N, int NA>
+__device__ __forceinline__ void rowbc_axpy(double (&a)[NA], double x, double c) {
+    static_assert((N == 6 || N == 9 || N == 12) && N <= NA, "chain lengths of the wave QP");
+    if constexpr (N == 6)
+        asm volatile("s_nop 1\n" DWBC_RB_AXPY_(0, 6, 7) DWBC_RB_AXPY_(1, 6, 7) DWBC_RB_AXPY_(2, 6, 7) DWBC_RB_AXPY_(3, 6, 7) DWBC_RB_AXPY_(4, 6, 7)
+                     DWBC_RB_AXPY_(5, 6, 7)
+                     : "+&v"(a[0]), "+&v"(a[1]), "+&v"(a[2]), "+&v"(a[3]), "+&v"(a[4]), "+&v"(a[5]) : "v"(x), "v"(c));
+    if constexpr (N == 9)
+        asm volatile("s_nop 1\n" DWBC_RB_AXPY_(0, 9, 10) DWBC_RB_AXPY_(1, 9, 10) DWBC_RB_AXPY_(2, 9, 10) DWBC_RB_AXPY_(3, 9, 10) DWBC_RB_AXPY_(4, 9, 10)
+                     DWBC_RB_AXPY_(5, 9, 10) DWBC_RB_AXPY_(6, 9, 10) DWBC_RB_AXPY_(7, 9, 10) DWBC_RB_AXPY_(8, 9, 10)
+                     : "+&v"(a[0]), "+&v"(a[1]), "+&v"(a[2]), "+&v"(a[3]), "+&v"(a[4]), "+&v"(a[5]), "+&v"(a[6]), "+&v"(a[7]), "+&v"(a[8]) : "v"(x), "v"(c));
+    if constexpr (N == 12)
+        asm volatile("s_nop 1\n" DWBC_RB_AXPY_(0, 12, 13) DWBC_RB_AXPY_(1, 12, 13) DWBC_RB_AXPY_(2, 12, 13) DWBC_RB_AXPY_(3, 12, 13)
+                     DWBC_RB_AXPY_(4, 12, 13) DWBC_RB_AXPY_(5, 12, 13) DWBC_RB_AXPY_(6, 12, 13) DWBC_RB_AXPY_(7, 12, 13) DWBC_RB_AXPY_(8, 12, 13)
+                     DWBC_RB_AXPY_(9, 12, 13) DWBC_RB_AXPY_(10, 12, 13) DWBC_RB_AXPY_(11, 12, 13)
+                     : "+&v"(a[0]), "+&v"(a[1]), "+&v"(a[2]), "+&v"(a[3]), "+&v"(a[4]), "+&v"(a[5]), "+&v"(a[6]), "+&v"(a[7]), "+&v"(a[8]), "+&v"(a[9]),
+                       "+&v"(a[10]), "+&v"(a[11])
+                     : "v"(x), "v"(c));
+}
+#undef DWBC_RB_DOT_
+#undef DWBC_RB_AXPY_
+// DPP row 0 copied to rows 1 - 3: v_permlane16_swap exchanges the odd rows of its first operand with the even rows of the second (on two
+// copies of x: rows 0 0 2 2), v_permlane32_swap the upper half of the first with the lower half of the second (rows 0 0 0 0); both
+// halves of the double.  Builtins: the compiler pads their hazard itself.
+__device__ __forceinline__ double row_replicate(double x) {
+    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+    const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const auto l32 = __builtin_amdgcn_permlane32_swap(l16[0], l16[0], false, false);
+    const auto h32 = __builtin_amdgcn_permlane32_swap(h16[0], h16[0], false, false);
+    return __hiloint2double((int)h32[0], (int)l32[0]);
+}
+}  // namespace dwbc
+#define ROWBC_FMA(J, acc, x, y) dwbc::rowbc_fma<J>((acc), (x), (y))
+#define ROWBC_DOT(N, acc, x, y) dwbc::rowbc_dot<N>((acc), (x), (y))
+#define ROWBC_AXPY(N, a, x, c) dwbc::rowbc_axpy<N>((a), (x), (c))
+#define ROW_REPLICATE(x) (x) = dwbc::row_replicate(x)
+#endif

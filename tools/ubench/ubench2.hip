@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
+#include <string>
 #include <vector>
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
@@ -30,7 +31,11 @@ __device__ __forceinline__ Stamp stamp() {
 // 10  32 x (ds_bpermute_b32 x2 + v_fma_f64)                   11  32 s_nop 0
 // 12  32 v_mul_f64                                             13  32 v_add_f64
 // 14  32 v_cndmask_b32                                         15  32 v_mov_b32
-// 16  v_fma_f64 with DPP row_newbcast? (not on gfx9) -> skipped
+// 16  32 v_fmac_f64_dpp row_newbcast, one dependent chain    17  32 v_fmac_f64_dpp row_newbcast, 8 independent accumulators
+//     (v_fma_f64 is VOP3 and has no DPP form; v_fmac_f64 is VOP2 and has one on gfx90a and later, with row_newbcast:n as its only control)
+// 18  32 x (2 v_mov_b32_dpp row_newbcast + s_nop 1 + v_fma_f64): what update_dpp on the two halves + fma compiles to
+// 19  8 x row replicate of a double (row 0 -> rows 1..3: v_permlane16_swap + v_permlane32_swap on both halves, from the builtins)
+// 20  8 x (s_nop 1 + 12 v_fmac_f64_dpp onto one accumulator): the 12-term dot product against a vector held one entry per lane
 template <int MODE>
 __global__ __launch_bounds__(64) void k_issue(const double* in, double* out, unsigned long long* cyc, int reps) {
     __shared__ double buf[128];
@@ -176,6 +181,62 @@ __global__ __launch_bounds__(64) void k_issue(const double* in, double* out, uns
         if constexpr (MODE == 15) {
             asm volatile(".rept 16\n v_mov_b32 %0, %2\n v_mov_b32 %1, %2\n .endr\n" : "=&v"(idx), "=&v"(f7) : "v"(lane));
         }
+        if constexpr (MODE == 16) {
+            asm volatile("s_nop 1\n .rept 32\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:3 row_mask:0xf bank_mask:0xf\n .endr\n" : "+v"(a0) : "v"(x), "v"(y));
+        }
+        if constexpr (MODE == 17) {
+            asm volatile(
+                "s_nop 1\n"
+                ".rept 4\n"
+                "v_fmac_f64_dpp %0, %8, %9 row_newbcast:3 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %1, %8, %9 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %2, %8, %9 row_newbcast:7 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %3, %8, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %4, %8, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %5, %8, %9 row_newbcast:13 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %6, %8, %9 row_newbcast:15 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %7, %8, %9 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                ".endr\n"
+                : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(x), "v"(y));
+        }
+        if constexpr (MODE == 18) {
+            int t0, t1;
+            asm volatile(
+                ".rept 4\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:3 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:3 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %0, %[t], %12, %0\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:5 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:5 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %1, %[t], %12, %1\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:7 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:7 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %2, %[t], %12, %2\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:9 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %3, %[t], %12, %3\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:11 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:11 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %4, %[t], %12, %4\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:13 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:13 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %5, %[t], %12, %5\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:15 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:15 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %6, %[t], %12, %6\n"
+                "v_mov_b32_dpp %8, %10 row_newbcast:1 row_mask:0xf bank_mask:0xf\n v_mov_b32_dpp %9, %11 row_newbcast:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n v_fma_f64 %7, %[t], %12, %7\n"
+                ".endr\n"
+                : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "=&v"(t0), "=&v"(t1)
+                : "v"(((int*)&x)[0]), "v"(((int*)&x)[1]), "v"(y), [t] "v"(x));
+            (void)t0; (void)t1;
+        }
+        if constexpr (MODE == 19) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                unsigned lo = (unsigned)__double2loint(a0), hi = (unsigned)__double2hiint(a0);
+                const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);  // [0]: rows 0 0 2 2
+                const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+                const auto l32 = __builtin_amdgcn_permlane32_swap(l16[0], l16[0], false, false);  // [0]: rows 0 0 0 0
+                const auto h32 = __builtin_amdgcn_permlane32_swap(h16[0], h16[0], false, false);
+                a0 = __hiloint2double((int)h32[0], (int)l32[0]);
+                asm volatile("" : "+v"(a0));
+            }
+        }
+        if constexpr (MODE == 20) {
+            asm volatile(
+                ".rept 8\n"
+                "s_nop 1\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:1 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:2 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:3 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:4 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:5 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:6 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:7 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:9 row_mask:0xf bank_mask:0xf\n"
+                "v_fmac_f64_dpp %0, %1, %2 row_newbcast:10 row_mask:0xf bank_mask:0xf\n v_fmac_f64_dpp %0, %1, %2 row_newbcast:11 row_mask:0xf bank_mask:0xf\n"
+                ".endr\n"
+                : "+v"(a0) : "v"(x), "v"(y));
+        }
     }
     Stamp s1 = stamp();
     if (lane == 0) { cyc[2 * blockIdx.x] = s1.cyc - s0.cyc; cyc[2 * blockIdx.x + 1] = s1.rt - s0.rt; }
@@ -254,7 +315,7 @@ static void med(std::vector<unsigned long long>& c, int G, double* cyc, double* 
     *cyc = (double)a[G / 2]; *rt = (double)b[G / 2];
 }
 
-int main() {
+int main(int argc, char** argv) {
     const int G0 = 1024;
     double *din, *dout; unsigned long long* dcyc;
     CK(hipMalloc(&din, 1 << 16)); CK(hipMalloc(&dout, 8 * G0 * 64 * 8)); CK(hipMalloc(&dcyc, 8 * G0 * 16));
@@ -267,16 +328,24 @@ int main() {
                         "v_pk_fma_f32 x32, 8 independent acc", "(2 v_readlane + s_nop 1 + v_fma_f64 sgpr) x32", "v_readlane_b32 x64",
                         "v_fma_f64 (SGPR-pair operand) x32", "(2 v_mov_dpp + s_nop 1 + v_fma_f64) x32", "(ds_read_b64 bcast + v_fma_f64) x32, 8 in flight",
                         "(ds_read_b128 bcast + 2 v_fma_f64) x16, 4 in flight", "(2 ds_bpermute + wait + v_fma_f64) x32 dependent", "s_nop 0 x32",
-                        "v_mul_f64 x32", "v_add_f64 x32", "v_cndmask_b32 x32", "v_mov_b32 x32"};
-    const int per[] = {32, 32, 32, 32, 32, 64, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32};
+                        "v_mul_f64 x32", "v_add_f64 x32", "v_cndmask_b32 x32", "v_mov_b32 x32",
+                        "v_fmac_f64_dpp row_newbcast x32, one dependent chain", "v_fmac_f64_dpp row_newbcast x32, 8 independent acc",
+                        "(2 v_mov_b32_dpp row_newbcast + s_nop 1 + v_fma_f64) x32", "row replicate of a double (4 permlane swaps) x8",
+                        "(s_nop 1 + 12 v_fmac_f64_dpp, one acc) x8, per FMA"};
+    const int per[] = {32, 32, 32, 32, 32, 64, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 32, 8, 96};
     typedef void (*issue_fn)(const double*, double*, unsigned long long*, int);
-    const issue_fn ifn[16] = {k_issue<0>, k_issue<1>, k_issue<2>, k_issue<3>, k_issue<4>, k_issue<5>, k_issue<6>, k_issue<7>,
-                              k_issue<8>, k_issue<9>, k_issue<10>, k_issue<11>, k_issue<12>, k_issue<13>, k_issue<14>, k_issue<15>};
+    const issue_fn ifn[21] = {k_issue<0>, k_issue<1>, k_issue<2>, k_issue<3>, k_issue<4>, k_issue<5>, k_issue<6>, k_issue<7>,
+                              k_issue<8>, k_issue<9>, k_issue<10>, k_issue<11>, k_issue<12>, k_issue<13>, k_issue<14>, k_issue<15>,
+                              k_issue<16>, k_issue<17>, k_issue<18>, k_issue<19>, k_issue<20>};
+    // `ubench2 rowbc`: the row-broadcast sheet only (modes 0, 1, 4, 9 as the yardstick beside 16 .. 20; one and two waves per SIMD)
+    const bool rowbc = argc > 1 && std::string(argv[1]) == "rowbc";
     printf("== issue cost (1024 x w single-wave workgroups), shader cycles per instruction group ==\n");
     for (int w : {1, 2, 4, 8}) {
+        if (rowbc && w > 2) break;
         const int G = G0 * w;
         printf("-- %d wave(s) per SIMD\n", w);
-        for (int mode = 0; mode < 16; mode++) {
+        for (int mode = 0; mode < 21; mode++) {
+            if (rowbc && !(mode == 0 || mode == 1 || mode == 4 || mode == 9 || mode >= 16)) continue;
             const int reps = 20000;
             for (int i = 0; i < 2; i++) ifn[mode]<<<G, 64>>>(din, dout, dcyc, reps);
             CK(hipDeviceSynchronize());
@@ -287,6 +356,7 @@ int main() {
             printf("%-58s %7.2f cyc each | clock %.2f GHz | %.2f ms\n", nm[mode], cy / ((double)reps * per[mode]), cy / rt * 0.1, ms);
         }
     }
+    if (rowbc) return 0;
     printf("== MFMA issue ==\n");
     typedef void (*mfma_fn)(const double*, double*, unsigned long long*, int);
     struct MF { int mode, nacc; mfma_fn fn; };
