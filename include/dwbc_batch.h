@@ -127,6 +127,13 @@ typedef struct dwbc_field_info {
 } dwbc_field_info;
 /* row `index` of the field table for the given sizes; 0 when index is past the end.  Needs no device and no batch. */
 int dwbc_field_describe(int index, const dwbc_field_dims *dims, dwbc_field_info *out);
+/* the lean launches below write outputs that are no dwbc_field: each family has an output enum and get / bind / bytes calls of its own.
+ * Their table (libdwbc_amd/csrc/dwbc_fields.h as well) is read like the field table: row `index` of `family` for a model of n dof and a
+ * link query of n_queried entries.
+ * out->id is the family's output enumerator, bindable 1, host_mirror 0; 0 when index is past the end or there is no such family.  Needs
+ * no device and no batch. */
+enum dwbc_lean_family { DWBC_LEAN_GRAV = 0, DWBC_LEAN_LINK_QUERY = 1, DWBC_LEAN_DYNAMICS = 2, DWBC_LEAN_CONTACT_SPACE = 3 };
+int dwbc_lean_output_describe(int family, int index, int n, int n_queried, dwbc_field_info *out);
 
 const char *dwbc_last_error(void);
 int dwbc_device_count(void);

@@ -68,6 +68,7 @@ SYMBOLS = [
     ("dwbc_batch_get", _i, [_vp, _i, _vp, C.c_size_t]),
     ("dwbc_batch_field_bytes", C.c_size_t, [_vp, _i]),
     ("dwbc_field_describe", _i, [_i, C.POINTER(FieldDims), C.POINTER(FieldInfo)]),
+    ("dwbc_lean_output_describe", _i, [_i, _i, _i, _i, C.POINTER(FieldInfo)]),
     ("dwbc_batch_launch_info", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("dwbc_batch_kernel_name", C.c_char_p, [_vp]),
     # generic hierarchical-QP class + LQP configurator

@@ -33,12 +33,6 @@ TASK_LINK_POSITION, TASK_LINK_POSITION_COM_FRAME, TASK_LINK_POSITION_CUSTOM_FRAM
 TASK_LINK_ROTATION, TASK_LINK_ROTATION_CUSTOM_FRAME = 6, 7
 SOLVE_HQP, SOLVE_INIT, SOLVE_REDUCED = 1, 2, 4
 REDIST_ADD_GRAVITY = 8  # a bit of the redistribution entry points' flags
-GRAV_OUTPUTS = {"tau": 0, "wrench": 1, "status": 2}  # enum dwbc_grav_output
-LINK_QUERY_OUTPUTS = {"pos": 0, "rot": 1, "vel": 2, "jac": 3}  # enum dwbc_link_query_output
-# enum dwbc_contact_space_output
-CONTACT_SPACE_OUTPUTS = {"J_C": 0, "Lambda_c": 1, "J_C_INV_T": 2, "N_C": 3, "A_inv_N_C": 4, "W": 5, "W_inv": 6, "NwJw": 7, "contact_pos": 8, "contact_rot": 9,
-                         "status": 10}
-DYNAMICS_OUTPUTS = {"A": 0, "A_inv": 1, "B": 2, "G": 3, "CMM": 4, "com": 5, "status": 6}  # enum dwbc_dynamics_output
 
 
 def describe(index, n, n_contacts, fstar_total, max_active):
@@ -48,11 +42,26 @@ def describe(index, n, n_contacts, fstar_total, max_active):
     return info if ok else None
 
 
+def describe_lean(family, index, n, n_queried):
+    """row `index` of a lean launch's outputs (same file) for a model of n dof and a link query of n_queried entries, None past the end"""
+    info = _lib.FieldInfo()
+    return info if _lib.load().dwbc_lean_output_describe(family, index, n, n_queried, C.byref(info)) else None
+
+
 # name -> field id of include/dwbc_batch.h, and name -> row of the table: read from the library once
 FIELDS, _ROW = {}, {}
 while (_r := describe(len(_ROW), 0, 0, 0, 0)) is not None:
     FIELDS[_r.name.decode()], _ROW[_r.name.decode()] = _r.id, len(_ROW)
 _DTYPES = (np.float64, np.int32, np.uint8)  # DWBC_ELEM_*
+# enum dwbc_lean_family, as the entry points (dwbc_batch_get_<family>, ...) and the keys of bound tensors spell it; per family
+# name -> enumerator of its output enum, read from the library once
+LEAN_FAMILIES = ("grav", "link_query", "dynamics", "contact_space")
+_LEAN = [{} for _ in LEAN_FAMILIES]
+for _f, _d in enumerate(_LEAN):
+    while (_r := describe_lean(_f, len(_d), 0, 0)) is not None:
+        _d[_r.name.decode()] = _r.id
+GRAV_OUTPUTS, LINK_QUERY_OUTPUTS, DYNAMICS_OUTPUTS, CONTACT_SPACE_OUTPUTS = _LEAN
+_GRAV, _LINK_QUERY, _DYNAMICS, _CONTACT_SPACE = range(4)
 
 
 class DwbcError(RuntimeError):
@@ -191,7 +200,7 @@ class Batch:
         self._keep = {}
         self._contact_consts = []  # (lx, ly, mu, mu_z) per registered contact and the batch-wide torque limit: what a missing half of
         self._tau_lim = None       # set_instance_params is filled from
-        self._link_query = (0, False)  # entries of set_link_query and whether it asked for Jacobians
+        self._link_query = 0  # entries of set_link_query
 
     # ---- setup (shared by all instances)
     def add_contact(self, link, point, lx, ly, mu=0.2, mu_z=0.2, contact_type=CONTACT_6D):
@@ -412,15 +421,60 @@ class Batch:
         _check(self._L.dwbc_batch_redistribute(self._h, (SOLVE_HQP if hqp else 0) | (SOLVE_INIT if init else 0) | (REDIST_ADD_GRAVITY if add_gravity else 0)))
 
     def time_redistributes(self, steps, add_gravity=False):
-        ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_redistribute(self._h, SOLVE_HQP | SOLVE_INIT | (REDIST_ADD_GRAVITY if add_gravity else 0), int(steps), C.byref(ms)))
-        return ms.value
+        return self._time("redistribute", steps, SOLVE_HQP | SOLVE_INIT | (REDIST_ADD_GRAVITY if add_gravity else 0))
 
     def redistribute_kernel_name(self):
-        name = self._L.dwbc_batch_redistribute_kernel_name(self._h).decode()
+        return self._kernel_name("redistribute")
+
+    # ---- what the lean launches share: `family` indexes LEAN_FAMILIES
+    def _kernel_name(self, which):
+        name = getattr(self._L, f"dwbc_batch_{which}_kernel_name")(self._h).decode()
         if not name:
             raise DwbcError(_lib.last_error())
         return name
+
+    def _time(self, which, steps, *flags):
+        """milliseconds of `steps` back-to-back launches behind one warm launch (dwbc_batch_time_<which>)"""
+        ms = C.c_float(0)
+        _check(getattr(self._L, f"dwbc_batch_time_{which}")(self._h, *flags, int(steps), C.byref(ms)))
+        return ms.value
+
+    def _lean_outputs(self, family):
+        """name -> (B, ...) array of every output the family's request holds, shaped and typed by the library's table.  With no request
+        the first output is asked for all the same: its refusal says what is missing."""
+        fam = LEAN_FAMILIES[family]
+        nbytes = {name: getattr(self._L, f"dwbc_batch_{fam}_bytes")(self._h, what) for name, what in _LEAN[family].items()}
+        out = {}
+        for name, what in _LEAN[family].items():
+            if nbytes[name] == 0 and any(nbytes.values()):
+                continue
+            r = describe_lean(family, what, self.n, self._link_query)
+            a = np.zeros((self.B,) + tuple(r.dims[: r.rank]), _DTYPES[r.dtype])
+            _check(getattr(self._L, f"dwbc_batch_get_{fam}")(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def _lean_bind(self, family, name, tensor):
+        fam, what = LEAN_FAMILIES[family], _LEAN[family][name]
+        bind = getattr(self._L, f"dwbc_batch_bind_{fam}")
+        if tensor is None:
+            _check(bind(self._h, what, None))
+            self._keep.pop(f"{fam}_{name}", None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = getattr(self._L, f"dwbc_batch_{fam}_bytes")(self._h, what)
+        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(bind(self._h, what, C.c_void_p(tensor.data_ptr())))
+        self._keep[f"{fam}_{name}"] = tensor
+
+    def _lean_set_outputs(self, family, names):
+        fam = LEAN_FAMILIES[family]
+        mask = 0
+        for k in names:
+            mask |= 1 << _LEAN[family][k]
+        _check(getattr(self._L, f"dwbc_batch_set_{fam}_outputs")(self._h, mask))
+        for k in _LEAN[family]:
+            self._keep.pop(f"{fam}_{k}", None)
 
     # ---- CalcGravCompensation on its own (reference include/dwbc.h:246-247, src/wbd.cpp:186-192)
     def grav_compensation(self):
@@ -429,44 +483,21 @@ class Batch:
         is.  No contact: zeros, status 1; more than two flags or a failed contact stage: zeros, status 0.  fp64, two contacts at most."""
         _check(self._L.dwbc_batch_grav_compensation(self._h))
 
-    def _grav_shape(self, name):
-        return {"tau": ((self.B, self.m), np.float64), "wrench": ((self.B, 12), np.float64), "status": ((self.B,), np.int32)}[name]
-
     def grav_outputs(self):
         """dict of ``tau`` (B, m), ``wrench`` (B, 12) zero padded and ``status`` (B,) int32 of the last grav_compensation() or
         redistribute(add_gravity=True); synchronises the stream"""
-        out = {}
-        for name, what in GRAV_OUTPUTS.items():
-            shape, dt = self._grav_shape(name)
-            a = np.zeros(shape, dt)
-            _check(self._L.dwbc_batch_get_grav(self._h, what, a.ctypes.data, a.nbytes))
-            out[name] = a
-        return out
+        return self._lean_outputs(_GRAV)
 
     def bind_grav(self, name, tensor):
         """output ``name`` ("tau", "wrench": float64; "status": int32) into a caller-owned device tensor, written in place by every later
         launch; None: back to a buffer of the batch's own"""
-        what = GRAV_OUTPUTS[name]
-        if tensor is None:
-            _check(self._L.dwbc_batch_bind_grav(self._h, what, None))
-            self._keep.pop("grav_" + name, None)
-            return
-        assert tensor.is_cuda and tensor.is_contiguous()
-        nbytes = self._L.dwbc_batch_grav_bytes(self._h, what)
-        assert tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
-        _check(self._L.dwbc_batch_bind_grav(self._h, what, C.c_void_p(tensor.data_ptr())))
-        self._keep["grav_" + name] = tensor
+        self._lean_bind(_GRAV, name, tensor)
 
     def grav_kernel_name(self):
-        name = self._L.dwbc_batch_grav_kernel_name(self._h).decode()
-        if not name:
-            raise DwbcError(_lib.last_error())
-        return name
+        return self._kernel_name("grav")
 
     def time_grav(self, steps):
-        ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_grav(self._h, int(steps), C.byref(ms)))
-        return ms.value
+        return self._time("grav", steps)
 
     # ---- UpdateKinematics on its own: poses, velocities and Jacobians of queried links before any f* is set
     def set_link_query(self, links, points=None, jacobians=False):
@@ -482,7 +513,7 @@ class Batch:
         _check(self._L.dwbc_batch_set_link_query(self._h, len(l), l.ctypes.data, p.ctypes.data if p is not None else None, 1 if jacobians else 0))
         for k in LINK_QUERY_OUTPUTS:
             self._keep.pop("link_query_" + k, None)
-        self._link_query = (len(l), bool(jacobians))
+        self._link_query = len(l)
 
     def update_kinematics(self):
         """One lean kernel on the batch's stream, asynchronous: forward kinematics of the state (and of qdot, if set_state got one; zero
@@ -490,53 +521,25 @@ class Batch:
         is; the three may be called in any order."""
         _check(self._L.dwbc_batch_update_kinematics(self._h))
 
-    def _link_query_shape(self, name):
-        n = self._link_query[0]
-        return {"pos": (self.B, n, 3), "rot": (self.B, n, 3, 3), "vel": (self.B, n, 6), "jac": (self.B, n, 6, self.n)}[name]
-
     def link_states(self):
         """dict of ``pos`` (B, L, 3), ``rot`` (B, L, 3, 3) row-major, ``vel`` (B, L, 6) = [v of the point; w] and, if the query asked for
         them, ``jac`` (B, L, 6, n) of the last update_kinematics(); synchronises the stream"""
-        out = {}
-        for name, what in LINK_QUERY_OUTPUTS.items():
-            if name == "jac" and not self._link_query[1]:
-                continue
-            a = np.zeros(self._link_query_shape(name))
-            _check(self._L.dwbc_batch_get_link_query(self._h, what, a.ctypes.data, a.nbytes))
-            out[name] = a
-        return out
+        return self._lean_outputs(_LINK_QUERY)
 
     def bind_link_query(self, name, tensor):
         """output ``name`` ("pos", "rot", "vel", "jac") of update_kinematics() into a caller-owned device tensor of float64, written in
         place by every later launch; None: back to a buffer of the batch's own"""
-        what = LINK_QUERY_OUTPUTS[name]
-        if tensor is None:
-            _check(self._L.dwbc_batch_bind_link_query(self._h, what, None))
-            self._keep.pop("link_query_" + name, None)
-            return
-        assert tensor.is_cuda and tensor.is_contiguous()
-        nbytes = self._L.dwbc_batch_link_query_bytes(self._h, what)
-        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
-        _check(self._L.dwbc_batch_bind_link_query(self._h, what, C.c_void_p(tensor.data_ptr())))
-        self._keep["link_query_" + name] = tensor
+        self._lean_bind(_LINK_QUERY, name, tensor)
 
     def link_query_kernel_name(self):
-        name = self._L.dwbc_batch_link_query_kernel_name(self._h).decode()
-        if not name:
-            raise DwbcError(_lib.last_error())
-        return name
+        return self._kernel_name("link_query")
 
     # ---- the dynamics half of UpdateKinematics on its own: rd_.A_, A_inv_, B_, G_, CMM_, com_pos (reference src/dwbc.cpp:279-371)
     def set_dynamics_outputs(self, names):
         """The outputs update_dynamics() writes: any of "A" (n, n), "A_inv" (n, n), "B" (n), "G" (n), "CMM" (6, n), "com" (3); "status" is
         always written.  What is not asked for is not computed: no "A_inv", no sweep; no "B", no RNEA; neither "CMM" nor "com", no centroidal
         block.  An empty list drops the request and its buffers.  A new request has new output buffers: bind tensors after it."""
-        mask = 0
-        for k in names:
-            mask |= 1 << DYNAMICS_OUTPUTS[k]
-        _check(self._L.dwbc_batch_set_dynamics_outputs(self._h, mask))
-        for k in DYNAMICS_OUTPUTS:
-            self._keep.pop("dynamics_" + k, None)
+        self._lean_set_outputs(_DYNAMICS, names)
 
     def update_dynamics(self):
         """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA and what the request asks for, from the state (and qdot, if
@@ -544,48 +547,21 @@ class Batch:
         redistribute(), grav_compensation() and update_kinematics() as it is; the five may be called in any order."""
         _check(self._L.dwbc_batch_update_dynamics(self._h))
 
-    def _dynamics_shape(self, name):
-        n = self.n
-        return {"A": ((self.B, n, n), np.float64), "A_inv": ((self.B, n, n), np.float64), "B": ((self.B, n), np.float64), "G": ((self.B, n), np.float64),
-                "CMM": ((self.B, 6, n), np.float64), "com": ((self.B, 3), np.float64), "status": ((self.B,), np.int32)}[name]
-
     def dynamics(self):
         """dict of the asked-for outputs and ``status`` (B,) int32 (0: "A_inv" was asked for and the sweep met a bad pivot; that instance's
         outputs are zero) of the last update_dynamics(); synchronises the stream"""
-        out = {}
-        for name, what in DYNAMICS_OUTPUTS.items():
-            if self._L.dwbc_batch_dynamics_bytes(self._h, what) == 0 and name != "status":
-                continue
-            shape, dt = self._dynamics_shape(name)
-            a = np.zeros(shape, dt)
-            _check(self._L.dwbc_batch_get_dynamics(self._h, what, a.ctypes.data, a.nbytes))
-            out[name] = a
-        return out
+        return self._lean_outputs(_DYNAMICS)
 
     def bind_dynamics(self, name, tensor):
         """asked-for output ``name`` of update_dynamics() into a caller-owned device tensor (float64; "status": int32), written in place by
         every later launch; None: back to a buffer of the batch's own"""
-        what = DYNAMICS_OUTPUTS[name]
-        if tensor is None:
-            _check(self._L.dwbc_batch_bind_dynamics(self._h, what, None))
-            self._keep.pop("dynamics_" + name, None)
-            return
-        assert tensor.is_cuda and tensor.is_contiguous()
-        nbytes = self._L.dwbc_batch_dynamics_bytes(self._h, what)
-        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
-        _check(self._L.dwbc_batch_bind_dynamics(self._h, what, C.c_void_p(tensor.data_ptr())))
-        self._keep["dynamics_" + name] = tensor
+        self._lean_bind(_DYNAMICS, name, tensor)
 
     def dynamics_kernel_name(self):
-        name = self._L.dwbc_batch_dynamics_kernel_name(self._h).decode()
-        if not name:
-            raise DwbcError(_lib.last_error())
-        return name
+        return self._kernel_name("dynamics")
 
     def time_dynamics(self, steps):
-        ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_dynamics(self._h, int(steps), C.byref(ms)))
-        return ms.value
+        return self._time("dynamics", steps)
 
     # ---- SetContact + CalcContactConstraint on their own: the contact-space members of RobotData (reference src/dwbc.cpp:433-478, src/wbd.cpp:108-143)
     def set_contact_space_outputs(self, names):
@@ -594,12 +570,7 @@ class Batch:
         written.  The shapes are fixed whatever the support: zero beyond the active contact dof.  What is not asked for is not computed: only
         "J_C" / the frames, no A^-1 sweep; no "W_inv", no 33-pivot sweep; no "N_C", no n x n product.  An empty list drops the request and its
         buffers.  A new request has new output buffers: bind tensors after it."""
-        mask = 0
-        for k in names:
-            mask |= 1 << CONTACT_SPACE_OUTPUTS[k]
-        _check(self._L.dwbc_batch_set_contact_space_outputs(self._h, mask))
-        for k in CONTACT_SPACE_OUTPUTS:
-            self._keep.pop("contact_space_" + k, None)
+        self._lean_set_outputs(_CONTACT_SPACE, names)
 
     def calc_contact_constraint(self):
         """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA, the contact stage and what the request asks for, from the
@@ -607,54 +578,24 @@ class Batch:
         redistribute(), grav_compensation(), update_kinematics() and update_dynamics() as it is; the six may be called in any order."""
         _check(self._L.dwbc_batch_calc_contact_constraint(self._h))
 
-    def _contact_space_shape(self, name):
-        n, m, B = self.n, self.n - 6, self.B
-        return {"J_C": ((B, 12, n), np.float64), "Lambda_c": ((B, 12, 12), np.float64), "J_C_INV_T": ((B, 12, n), np.float64), "N_C": ((B, n, n), np.float64),
-                "A_inv_N_C": ((B, n, n), np.float64), "W": ((B, m, m), np.float64), "W_inv": ((B, m, m), np.float64), "NwJw": ((B, m, 6), np.float64),
-                "contact_pos": ((B, 2, 3), np.float64), "contact_rot": ((B, 2, 3, 3), np.float64), "status": ((B,), np.int32)}[name]
-
     def contact_space(self):
         """dict of the asked-for outputs and ``status`` (B,) int32 (the return value of CalcContactConstraint; 0: that instance's outputs
         are zero) of the last calc_contact_constraint(); synchronises the stream"""
-        out = {}
-        for name, what in CONTACT_SPACE_OUTPUTS.items():
-            if self._L.dwbc_batch_contact_space_bytes(self._h, what) == 0 and name != "status":
-                continue
-            shape, dt = self._contact_space_shape(name)
-            a = np.zeros(shape, dt)
-            _check(self._L.dwbc_batch_get_contact_space(self._h, what, a.ctypes.data, a.nbytes))
-            out[name] = a
-        return out
+        return self._lean_outputs(_CONTACT_SPACE)
 
     def bind_contact_space(self, name, tensor):
         """asked-for output ``name`` of calc_contact_constraint() into a caller-owned device tensor (float64; "status": int32), written in
         place by every later launch; None: back to a buffer of the batch's own"""
-        what = CONTACT_SPACE_OUTPUTS[name]
-        if tensor is None:
-            _check(self._L.dwbc_batch_bind_contact_space(self._h, what, None))
-            self._keep.pop("contact_space_" + name, None)
-            return
-        assert tensor.is_cuda and tensor.is_contiguous()
-        nbytes = self._L.dwbc_batch_contact_space_bytes(self._h, what)
-        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
-        _check(self._L.dwbc_batch_bind_contact_space(self._h, what, C.c_void_p(tensor.data_ptr())))
-        self._keep["contact_space_" + name] = tensor
+        self._lean_bind(_CONTACT_SPACE, name, tensor)
 
     def contact_space_kernel_name(self):
-        name = self._L.dwbc_batch_contact_space_kernel_name(self._h).decode()
-        if not name:
-            raise DwbcError(_lib.last_error())
-        return name
+        return self._kernel_name("contact_space")
 
     def time_contact_space(self, steps):
-        ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_contact_space(self._h, int(steps), C.byref(ms)))
-        return ms.value
+        return self._time("contact_space", steps)
 
     def time_solves(self, steps, reduced=False):
-        ms = C.c_float(0)
-        _check(self._L.dwbc_batch_time_solves(self._h, SOLVE_HQP | SOLVE_INIT | (SOLVE_REDUCED if reduced else 0), int(steps), C.byref(ms)))
-        return ms.value
+        return self._time("solves", steps, SOLVE_HQP | SOLVE_INIT | (SOLVE_REDUCED if reduced else 0))
 
     def launch_info(self):
         t, l = C.c_int(0), C.c_int(0)

@@ -255,14 +255,20 @@ static dwbc_field_dims field_dims(const dwbc_batch *b) { return dwbc_field_dims{
 int dwbc_field_describe(int index, const dwbc_field_dims *dims, dwbc_field_info *out) {
     if (index < 0 || index >= fld::kRowCount || !dims || !out) return 0;
     const fld::Row &r = fld::kRows[index];
-    *out = dwbc_field_info{r.id, r.name, r.type, r.shape.rank, {1, 1, 1}, fld::elements(r, *dims) * fld::item_size(r.type), (r.flags & fld::kBindable) != 0, (r.flags & fld::kMirror) != 0};
-    for (int i = 0; i < r.shape.rank; i++) out->dims[i] = fld::extent(r.shape.dim[i], *dims);
+    *out = fld::describe(r.id, r.name, r.type, r.shape, *dims, 0, (r.flags & fld::kBindable) != 0, (r.flags & fld::kMirror) != 0);
+    return 1;
+}
+
+int dwbc_lean_output_describe(int family, int index, int n, int n_queried, dwbc_field_info *out) {
+    if (family < 0 || family >= fld::kLeanCount || index < 0 || index >= fld::kLean[family].count || !out) return 0;
+    const fld::LeanRow &r = fld::kLean[family].rows[index];
+    *out = fld::describe(r.id, r.name, r.type, r.shape, dwbc_field_dims{n, 0, 0, 0}, n_queried, true, false);
     return 1;
 }
 
 size_t dwbc_batch_field_bytes(const dwbc_batch *b, int field) {
     const fld::Row *r = fld::find(field);
-    return r ? (size_t)b->B * fld::elements(*r, field_dims(b)) * fld::item_size(r->type) : 0;
+    return r ? (size_t)b->B * fld::elements(r->shape, field_dims(b)) * fld::item_size(r->type) : 0;
 }
 
 // ---- the buffer slots (dwbc_batch::buf).  The batch's device is current in all three.
@@ -601,7 +607,7 @@ int dwbc_batch_set_max_active_contacts(dwbc_batch *b, int n) {
     // the new buffer first, the swap only on success: a failed allocation leaves the batch as it was
     dwbc_field_dims dims = field_dims(b);
     dims.max_active = n;
-    const size_t bytes = (size_t)b->B * fld::elements(*fld::find(DWBC_WRENCH), dims) * sizeof(double);
+    const size_t bytes = (size_t)b->B * fld::elements(fld::find(DWBC_WRENCH)->shape, dims) * sizeof(double);
     void *nw = nullptr;
     HIP_OK(hipMalloc(&nw, bytes));
     if (hipMemset(nw, 0, bytes) != hipSuccess) {
@@ -656,11 +662,15 @@ int dwbc_batch_enable_dump(dwbc_batch *b, int on) {
     return 1;
 }
 
-static int upload_inputs(dwbc_batch *b) {
+// the mirrors of these slots that are newer than their device buffers, in this order
+static int send_inputs(dwbc_batch *b, std::initializer_list<int> slots) {
     bool queued = false;
-    for (const int slot : {fld::kTraj, fld::kCustom, fld::kCtime, fld::kInstPar, fld::kQdot, fld::kQ, fld::kFlags, fld::kFstar})
+    for (const int slot : slots)
         if (!send(b, slot, &queued)) return 0;
     return queued ? mark_upload(b) : 1;
+}
+static int upload_inputs(dwbc_batch *b) {  // what the cycle reads
+    return send_inputs(b, {fld::kTraj, fld::kCustom, fld::kCtime, fld::kInstPar, fld::kQdot, fld::kQ, fld::kFlags, fld::kFstar});
 }
 
 // the set-up a launch hands to the kernel: with a per-instance parameter record the torque rows exist as after dwbc_batch_set_torque_limit
@@ -671,15 +681,22 @@ static const Setup *launch_setup(const dwbc_batch *b, const BatchIO &io, Setup &
     return &tmp;
 }
 
-// one launch of the cycle: the planner picks the build, whatever its arithmetic type or kind
-static int launch(dwbc_batch *b, bool reduced) {
-    const dwbc_plan::Plan p = dwbc_plan::plan(plan_request(b, reduced), b->tables, b->n_tables);
-    if (!p.row) return fail(p.err);
+// the kernel of an accepted plan on the batch's stream, one workgroup per instance; its dynamic-LDS attribute is raised once per kernel
+// and batch
+static int launch_kernel(dwbc_batch *b, const dwbc_plan::Plan &p, void **args) {
     const void *fn = p.row->fn;
     if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
         HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
         b->lds_attr_set.push_back(fn);
     }
+    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    return 1;
+}
+
+// one launch of the cycle: the planner picks the build, whatever its arithmetic type or kind
+static int launch(dwbc_batch *b, bool reduced) {
+    const dwbc_plan::Plan p = dwbc_plan::plan(plan_request(b, reduced), b->tables, b->n_tables);
+    if (!p.row) return fail(p.err);
     // the fp32 kernels read and write the double buffers of the boundary themselves (io_t); only the model table is kept in float
     const bool f32 = b->dtype == DWBC_F32;
     if (f32 && !b->f_body) {
@@ -711,7 +728,7 @@ static int launch(dwbc_batch *b, bool reduced) {
     io.inst_par = b->dev<double>(fld::kInstPar);
     Setup su_rec;
     void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io};
-    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
+    if (!launch_kernel(b, p, args)) return 0;
     b->ws_valid = p.ws_valid_after;
     b->last = p;
     return 1;
@@ -757,65 +774,153 @@ static dwbc_plan::Plan redist_plan(const dwbc_batch *b, bool hqp) {
     return dwbc_plan::plan(q, b->tables, b->n_tables);
 }
 
-static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
-    const void *fn = p.row->fn;
-    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        b->lds_attr_set.push_back(fn);
+// ---- what the lean launches share (enum dwbc_lean_family; their outputs: dwbc_fields::kLean).  Per family there remain the kernel's IO
+// records, the inputs it uploads and its preconditions
+static dwbc_plan::Plan lean_plan(const dwbc_batch *b, int family) {
+    static constexpr bool dwbc_plan::Request::*kind[] = {&dwbc_plan::Request::grav_comp, &dwbc_plan::Request::link_query, &dwbc_plan::Request::dynamics,
+                                                         &dwbc_plan::Request::contact_space};
+    dwbc_plan::Request q = plan_request(b, false);
+    q.*kind[family] = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+
+// name of a plan's kernel as rocprofv3 prints the instantiation, "" with the error set for a refused one; a string per family (and one, at
+// the end, for the redistribution) and thread
+static const char *plan_name(const dwbc_plan::Plan &p, int which) {
+    static thread_local char name[fld::kLeanCount + 1][160];
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name[which], sizeof name[which]);
+    return name[which];
+}
+
+// bytes of all B instances of one output under the family's request (0: not part of it, no such output)
+static size_t lean_bytes(const dwbc_batch *b, int family, int what) {
+    const fld::Family &f = fld::kLean[family];
+    if (what < 0 || what >= f.count || !((b->lean[family].mask >> what) & 1u)) return 0;
+    return (size_t)b->B * fld::elements(f.rows[what].shape, field_dims(b), b->lq_n) * fld::item_size(f.rows[what].type);
+}
+
+// why output `what` of the family cannot be named (nullptr: it can)
+static const char *lean_refusal(const dwbc_batch *b, int family, int what) {
+    const fld::Family &f = fld::kLean[family];
+    if (what < 0 || what >= f.count) return f.unknown;
+    if (!b->lean[family].mask) return f.no_request;
+    if (!((b->lean[family].mask >> what) & 1u)) return f.not_asked;
+    return nullptr;
+}
+
+static int read_back(dwbc_batch *b, const void *src, void *out, size_t nbytes);
+static int lean_get(dwbc_batch *b, int family, int what, void *out, size_t bytes) {
+    if (const char *why = lean_refusal(b, family, what)) return fail(why);
+    if (!b->lean[family].ran) return fail(fld::kLean[family].not_run);
+    const size_t need = lean_bytes(b, family, what);
+    if (bytes < need) return fail("output buffer too small");
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kLean[family].rows[what].slot].d, out, need);
+}
+
+static int lean_bind(dwbc_batch *b, int family, int what, void *p) {
+    if (const char *why = lean_refusal(b, family, what)) return fail(why);
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kLean[family].rows[what].slot];
+    release(u);
+    b->lean[family].ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, lean_bytes(b, family, what));
+    u.d = p;
+    return 1;
+}
+
+// the outputs of the family's request exist (bound ones stay bound)
+static int lean_ensure(dwbc_batch *b, int family) {
+    for (int w = 0; w < fld::kLean[family].count; w++)
+        if (const size_t bytes = lean_bytes(b, family, w))
+            if (!ensure(b->buf[fld::kLean[family].rows[w].slot], bytes)) return 0;
+    return 1;
+}
+
+// a new request: outputs of the new sizes, owned by the batch (a buffer bound for the old request may be too small for the new one);
+// allocated here, so that the launch itself allocates nothing
+static int lean_request(dwbc_batch *b, int family, unsigned mask) {
+    HIP_OK(hipSetDevice(b->device));
+    for (int w = 0; w < fld::kLean[family].count; w++) release(b->buf[fld::kLean[family].rows[w].slot]);  // (hipFree waits for the launches that write them)
+    b->lean[family].mask = mask;
+    b->lean[family].ran = false;
+    return lean_ensure(b, family);
+}
+
+// dwbc_batch_set_*_outputs: a refused mask leaves the request and the outputs of the batch as they were
+static int lean_set_outputs(dwbc_batch *b, int family, unsigned mask) {
+    const fld::Family &f = fld::kLean[family];
+    if (mask & ~f.all()) return fail(f.unknown_bit);
+    if (mask) {
+        const dwbc_plan::Plan p = lean_plan(b, family);
+        if (!p.row) return fail(p.err);
+        mask |= 1u << f.status;
     }
-    BatchIO io{};  // what stage 0 and the contact stage read; no output of the cycle is named
+    return lean_request(b, family, mask);
+}
+
+// what every lean kernel reads: the state and the model
+static BatchIO lean_io(const dwbc_batch *b) {
+    BatchIO io{};
     io.B = b->B;
     io.q = b->dev<double>(fld::kQ);
-    io.flags = b->dev<unsigned char>(fld::kFlags);
-    io.fstar = b->dev<double>(fld::kFstar);
     io.body = b->d_body;
     io.topo = b->d_topo;
-    io.hqp = 1;
     io.pair_swap_bit = -1;
+    return io;
+}
+
+// dwbc_batch_time_*: first() -- uploads and one warm launch -- then K launches by again(), bracketed by HIP events on the batch's stream;
+// the events are destroyed on every way out (a failed step has set the error string)
+extern "C++" {
+template <class First, class Again>
+static int time_launches(dwbc_batch *b, int steps, float *ms, First first, Again again) {
+    HIP_OK(hipSetDevice(b->device));
+    if (!first()) return 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&]() -> int {
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, b->stream));
+        for (int i = 0; i < steps; i++)
+            if (!again()) return 0;
+        HIP_OK(hipEventRecord(e1, b->stream));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(ms, e0, e1));
+        return 1;
+    };
+    const int ok = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+}
+
+int dwbc_batch_time_solves(dwbc_batch *b, unsigned flags, int steps, float *ms) {
+    return time_launches(b, steps, ms, [&] { return dwbc_batch_solve(b, flags); }, [&] { return launch(b, flags & DWBC_SOLVE_REDUCED); });
+}
+
+static int launch_redistribute(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    BatchIO io = lean_io(b);  // what stage 0 and the contact stage read; no output of the cycle is named
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.fstar = b->dev<double>(fld::kFstar);
+    io.hqp = 1;
     io.inst_par = b->dev<double>(fld::kInstPar);
     Setup su_rec;
     RedistIO rio{b->dev<double>(fld::kTauIn), b->dev<double>(fld::kRdTau), b->dev<double>(fld::kRdCf), b->dev<double>(fld::kRdWrench), b->dev<int>(fld::kRdStatus)};
     void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io, (void *)&rio};
-    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
-    return 1;
+    return launch_kernel(b, p, args);
 }
 
-static int read_back(dwbc_batch *b, const void *src, void *out, size_t nbytes);
 // ---- CalcGravCompensation on its own, or ahead of the redistribution of a command on top of it: dwbc_redistribute.h with GRAV = true
-static dwbc_plan::Plan grav_plan(const dwbc_batch *b) {
-    dwbc_plan::Request q = plan_request(b, false);
-    q.grav_comp = true;
-    return dwbc_plan::plan(q, b->tables, b->n_tables);
-}
-
-size_t dwbc_batch_grav_bytes(const dwbc_batch *b, int what) {
-    const size_t per[3] = {(size_t)b->m * sizeof(double), 12 * sizeof(double), sizeof(int)};
-    return what >= DWBC_GRAV_TAU && what <= DWBC_GRAV_STATUS ? (size_t)b->B * per[what] : 0;
-}
-
-// the outputs exist before the first launch writes them (bound ones stay bound)
-static int ensure_grav_outputs(dwbc_batch *b) {
-    for (int w = DWBC_GRAV_TAU; w <= DWBC_GRAV_STATUS; w++)
-        if (!b->buf[fld::kGvTau + w].d && !ensure(b->buf[fld::kGvTau + w], dwbc_batch_grav_bytes(b, w))) return 0;
-    return 1;
-}
-
 // with_input: the redistribution of torque_grav_ + torque input goes with it
 static int launch_grav(dwbc_batch *b, const dwbc_plan::Plan &p, bool with_input) {
-    const void *fn = p.row->fn;
-    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        b->lds_attr_set.push_back(fn);
-    }
-    BatchIO io{};  // what stage 0 and the contact stage read; no buffer of the cycle or of the link query is named
-    io.B = b->B;
-    io.q = b->dev<double>(fld::kQ);
+    BatchIO io = lean_io(b);  // what stage 0 and the contact stage read; no buffer of the cycle or of the link query is named
     io.flags = b->dev<unsigned char>(fld::kFlags);
     io.fstar = b->dev<double>(fld::kFstar);
-    io.body = b->d_body;
-    io.topo = b->d_topo;
     io.hqp = 1;
-    io.pair_swap_bit = -1;
     io.inst_par = with_input ? b->dev<double>(fld::kInstPar) : nullptr;  // (QP rows alone read the record)
     Setup su_rec;
     GravIO gio{};
@@ -830,82 +935,32 @@ static int launch_grav(dwbc_batch *b, const dwbc_plan::Plan &p, bool with_input)
     gio.wrench = b->dev<double>(fld::kGvWrench);
     gio.status = b->dev<int>(fld::kGvStatus);
     void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io, (void *)&gio};
-    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
-    b->gv_ran = true;
+    if (!launch_kernel(b, p, args)) return 0;
+    b->lean[DWBC_LEAN_GRAV].ran = true;
     return 1;
 }
 
 // uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
 static int grav_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
-    const dwbc_plan::Plan p = grav_plan(b);
+    const dwbc_plan::Plan p = lean_plan(b, DWBC_LEAN_GRAV);
     if (!p.row) return fail(p.err);
     if (b->su.n_contacts < 1) return fail("no contact constraint");
     HIP_OK(hipSetDevice(b->device));
     if (!upload_inputs(b)) return 0;  // (the state and the flags are read; stage 0 stages f* of a batch that has task levels)
-    if (!ensure_grav_outputs(b)) return 0;
+    if (!lean_ensure(b, DWBC_LEAN_GRAV)) return 0;  // (the one family whose outputs are not allocated by a request)
     if (planned) *planned = p;
     return launch_grav(b, p, false);
 }
 
 int dwbc_batch_grav_compensation(dwbc_batch *b) { return grav_once(b, nullptr); }
-
-// K launches bracketed by HIP events on the batch's stream; the events are destroyed on every way out (a failed step has set the error string)
-// mode 0: the plain redistribution, 1: gravity compensation alone, 2: gravity compensation and the redistribution on top of it
-static int time_launches(dwbc_batch *b, int steps, float *ms, const dwbc_plan::Plan &p, int mode) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto timed = [&]() -> int {
-        HIP_OK(hipEventCreate(&e0));
-        HIP_OK(hipEventCreate(&e1));
-        HIP_OK(hipEventRecord(e0, b->stream));
-        for (int i = 0; i < steps; i++)
-            if (!(mode == 0 ? launch_redistribute(b, p) : launch_grav(b, p, mode == 2))) return 0;
-        HIP_OK(hipEventRecord(e1, b->stream));
-        HIP_OK(hipEventSynchronize(e1));
-        HIP_OK(hipEventElapsedTime(ms, e0, e1));
-        return 1;
-    };
-    const int ok = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return ok;
-}
-
 int dwbc_batch_time_grav(dwbc_batch *b, int steps, float *ms) {
-    HIP_OK(hipSetDevice(b->device));
     dwbc_plan::Plan p{};
-    if (!grav_once(b, &p)) return 0;  // uploads + warm launch
-    return time_launches(b, steps, ms, p, 1);
+    return time_launches(b, steps, ms, [&] { return grav_once(b, &p); }, [&] { return launch_grav(b, p, false); });
 }
-
-const char *dwbc_batch_grav_kernel_name(const dwbc_batch *b) {
-    static thread_local char name[160];
-    const dwbc_plan::Plan p = grav_plan(b);
-    if (!p.row) { fail(p.err); return ""; }
-    dwbc_plan::format_name(*p.row, name, sizeof name);
-    return name;
-}
-
-int dwbc_batch_get_grav(dwbc_batch *b, int what, void *out, size_t bytes) {
-    const size_t need = dwbc_batch_grav_bytes(b, what);
-    if (need == 0) return fail("gravity compensation: unknown output");
-    if (!b->gv_ran) return fail("no gravity-compensation output yet: call dwbc_batch_grav_compensation (or dwbc_batch_redistribute with DWBC_REDIST_ADD_GRAVITY) first");
-    if (bytes < need) return fail("output buffer too small");
-    HIP_OK(hipSetDevice(b->device));
-    HIP_OK(hipStreamSynchronize(b->stream));
-    return read_back(b, b->buf[fld::kGvTau + what].d, out, need);
-}
-
-int dwbc_batch_bind_grav(dwbc_batch *b, int what, void *p) {
-    const size_t need = dwbc_batch_grav_bytes(b, what);
-    if (need == 0) return fail("gravity compensation: unknown output");
-    HIP_OK(hipSetDevice(b->device));
-    Buf &u = b->buf[fld::kGvTau + what];
-    release(u);
-    b->gv_ran = false;  // (what the batch's own buffer held is not in the new one)
-    if (!p) return ensure(u, need);
-    u.d = p;
-    return 1;
-}
+size_t dwbc_batch_grav_bytes(const dwbc_batch *b, int what) { return lean_bytes(b, DWBC_LEAN_GRAV, what); }
+int dwbc_batch_get_grav(dwbc_batch *b, int what, void *out, size_t bytes) { return lean_get(b, DWBC_LEAN_GRAV, what, out, bytes); }
+int dwbc_batch_bind_grav(dwbc_batch *b, int what, void *p) { return lean_bind(b, DWBC_LEAN_GRAV, what, p); }
+const char *dwbc_batch_grav_kernel_name(const dwbc_batch *b) { return plan_name(lean_plan(b, DWBC_LEAN_GRAV), DWBC_LEAN_GRAV); }
 
 // uploads whatever is pending, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
 // DWBC_REDIST_ADD_GRAVITY: every refusal of the plain redistribution first, then the gravity-compensation kernel in its place
@@ -917,35 +972,24 @@ static int redistribute_once(dwbc_batch *b, unsigned flags, dwbc_plan::Plan *pla
     if (b->su.n_contacts < 1) return fail("no contact constraint");
     if (!b->tau_in_set) return fail("no torque input: call dwbc_batch_set_torque_input (or bind DWBC_IN_TORQUE) first");
     const bool grav = (flags & DWBC_REDIST_ADD_GRAVITY) != 0;
-    if (grav && !(p = grav_plan(b)).row) return fail(p.err);
+    if (grav && !(p = lean_plan(b, DWBC_LEAN_GRAV)).row) return fail(p.err);
     HIP_OK(hipSetDevice(b->device));
     if (!upload_inputs(b)) return 0;
-    bool queued = false;
-    if (!send(b, fld::kTauIn, &queued)) return 0;
-    if (queued && !mark_upload(b)) return 0;
+    if (!send_inputs(b, {fld::kTauIn})) return 0;
     for (const int f : {DWBC_REDIST_TAU, DWBC_REDIST_CF, DWBC_REDIST_WRENCH, DWBC_REDIST_STATUS})
         if (!ensure_field(b, f)) return 0;
-    if (grav && !ensure_grav_outputs(b)) return 0;
+    if (grav && !lean_ensure(b, DWBC_LEAN_GRAV)) return 0;
     if (planned) *planned = p;
     return grav ? launch_grav(b, p, true) : launch_redistribute(b, p);
 }
 
 int dwbc_batch_redistribute(dwbc_batch *b, unsigned flags) { return redistribute_once(b, flags, nullptr); }
-
 int dwbc_batch_time_redistribute(dwbc_batch *b, unsigned flags, int steps, float *ms) {
-    HIP_OK(hipSetDevice(b->device));
     dwbc_plan::Plan p{};
-    if (!redistribute_once(b, flags, &p)) return 0;  // uploads + warm launch
-    return time_launches(b, steps, ms, p, (flags & DWBC_REDIST_ADD_GRAVITY) ? 2 : 0);
+    const bool grav = (flags & DWBC_REDIST_ADD_GRAVITY) != 0;
+    return time_launches(b, steps, ms, [&] { return redistribute_once(b, flags, &p); }, [&] { return grav ? launch_grav(b, p, true) : launch_redistribute(b, p); });
 }
-
-const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b) {
-    static thread_local char name[160];
-    const dwbc_plan::Plan p = redist_plan(b, true);
-    if (!p.row) { fail(p.err); return ""; }
-    dwbc_plan::format_name(*p.row, name, sizeof name);
-    return name;
-}
+const char *dwbc_batch_redistribute_kernel_name(const dwbc_batch *b) { return plan_name(redist_plan(b, true), fld::kLeanCount); }
 
 int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     // RobotData::CopyKinematicsData (reference src/dwbc.cpp:1711-1762): state, contacts (with their flags), task spaces (with
@@ -997,23 +1041,6 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
 int dwbc_batch_sync(dwbc_batch *b) {
     HIP_OK(hipSetDevice(b->device));
     HIP_OK(hipStreamSynchronize(b->stream));
-    return 1;
-}
-
-int dwbc_batch_time_solves(dwbc_batch *b, unsigned flags, int steps, float *ms) {
-    HIP_OK(hipSetDevice(b->device));
-    if (!dwbc_batch_solve(b, flags)) return 0;  // uploads + warm launch
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0));
-    HIP_OK(hipEventCreate(&e1));
-    HIP_OK(hipEventRecord(e0, b->stream));
-    for (int i = 0; i < steps; i++)
-        if (!launch(b, flags & DWBC_SOLVE_REDUCED)) return 0;
-    HIP_OK(hipEventRecord(e1, b->stream));
-    HIP_OK(hipEventSynchronize(e1));
-    HIP_OK(hipEventElapsedTime(ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     return 1;
 }
 
@@ -1073,20 +1100,6 @@ int dwbc_batch_launch_info(const dwbc_batch *b, int *threads, int *lds) {
 }
 
 // ---- UpdateKinematics on its own for a set of queried links: the lean kernel of dwbc_link_query.h
-static dwbc_plan::Plan link_query_plan(const dwbc_batch *b) {
-    dwbc_plan::Request q = plan_request(b, false);
-    q.link_query = true;
-    return dwbc_plan::plan(q, b->tables, b->n_tables);
-}
-
-// doubles per instance of one output of the query as it stands (0: no such output)
-static size_t link_query_elems(const dwbc_batch *b, int what) {
-    const size_t per[4] = {3, 9, 6, b->lq_jac ? (size_t)6 * b->n : 0};
-    return what >= DWBC_LQ_POS && what <= DWBC_LQ_JAC ? b->lq_n * per[what] : 0;
-}
-
-size_t dwbc_batch_link_query_bytes(const dwbc_batch *b, int what) { return (size_t)b->B * link_query_elems(b, what) * sizeof(double); }
-
 int dwbc_batch_set_link_query(dwbc_batch *b, int n, const int32_t *links, const double *points, int want_jacobians) {
     if (n < 0 || n > kMaxLinkQuery) return fail("link query: at most 16 entries");
     if (n > 0 && !links) return fail("link query: links is NULL");
@@ -1097,47 +1110,32 @@ int dwbc_batch_set_link_query(dwbc_batch *b, int n, const int32_t *links, const 
             return fail("link query: the COM link takes no point");
     }
     if (n > 0) {
-        const dwbc_plan::Plan p = link_query_plan(b);
+        const dwbc_plan::Plan p = lean_plan(b, DWBC_LEAN_LINK_QUERY);
         if (!p.row) return fail(p.err);
     }
-    // outputs of the new size, owned by the batch (a buffer bound for the old query may be too small for the new one); allocated here, so
-    // that dwbc_batch_update_kinematics itself allocates nothing
-    HIP_OK(hipSetDevice(b->device));
-    for (int w = DWBC_LQ_POS; w <= DWBC_LQ_JAC; w++) release(b->buf[fld::kLqPos + w]);  // (hipFree waits for the launches that write them)
-    b->lq_n = n;
-    b->lq_jac = n > 0 && want_jacobians != 0;
-    b->lq_ran = false;
+    b->lq_n = n;  // (sizes the outputs of the request below)
     for (int i = 0; i < n; i++) {
         b->lq_link[i] = links[i];
         for (int a = 0; a < 3; a++) b->lq_point[i][a] = points ? points[3 * i + a] : 0.0;
     }
-    for (int w = DWBC_LQ_POS; w <= DWBC_LQ_JAC; w++)
-        if (const size_t bytes = dwbc_batch_link_query_bytes(b, w))
-            if (!ensure(b->buf[fld::kLqPos + w], bytes)) return 0;
-    return 1;
+    unsigned mask = n > 0 ? fld::kLean[DWBC_LEAN_LINK_QUERY].all() : 0u;  // an empty query drops the request and its buffers
+    if (!want_jacobians) mask &= ~(1u << DWBC_LQ_JAC);
+    return lean_request(b, DWBC_LEAN_LINK_QUERY, mask);
 }
 
 int dwbc_batch_update_kinematics(dwbc_batch *b) {
-    if (b->lq_n < 1) return fail("no link query: call dwbc_batch_set_link_query first");
-    const dwbc_plan::Plan p = link_query_plan(b);
+    if (!b->lean[DWBC_LEAN_LINK_QUERY].mask) return fail(fld::kLean[DWBC_LEAN_LINK_QUERY].no_request);
+    const dwbc_plan::Plan p = lean_plan(b, DWBC_LEAN_LINK_QUERY);
     if (!p.row) return fail(p.err);
     HIP_OK(hipSetDevice(b->device));
-    bool queued = false;
-    for (const int slot : {fld::kQdot, fld::kQ})
-        if (!send(b, slot, &queued)) return 0;
-    if (queued && !mark_upload(b)) return 0;
-    BatchIO io{};  // the state and the model; no buffer of the cycle or of the redistribution is named
-    io.B = b->B;
-    io.q = b->dev<double>(fld::kQ);
+    if (!send_inputs(b, {fld::kQdot, fld::kQ})) return 0;
+    BatchIO io = lean_io(b);  // the state and the model; no buffer of the cycle or of the redistribution is named
     io.qdot = b->dev<double>(fld::kQdot);
-    io.body = b->d_body;
-    io.topo = b->d_topo;
-    io.pair_swap_bit = -1;
     LinkQueryIO lq{};
     lq.n = b->lq_n;
     lq.nb = b->su.nb;
     lq.maxdepth = b->su.maxdepth;
-    lq.want_jac = b->lq_jac ? 1 : 0;
+    lq.want_jac = (b->lean[DWBC_LEAN_LINK_QUERY].mask >> DWBC_LQ_JAC) & 1u;
     for (int i = 0; i < b->lq_n; i++) {
         lq.link[i] = b->lq_link[i];
         lq.has_com = lq.has_com || b->lq_link[i] == b->su.nb;
@@ -1146,103 +1144,26 @@ int dwbc_batch_update_kinematics(dwbc_batch *b) {
     lq.pos = b->dev<double>(fld::kLqPos);
     lq.rot = b->dev<double>(fld::kLqRot);
     lq.vel = b->dev<double>(fld::kLqVel);
-    lq.jac = b->lq_jac ? b->dev<double>(fld::kLqJac) : nullptr;
+    lq.jac = lq.want_jac ? b->dev<double>(fld::kLqJac) : nullptr;
     void *args[] = {(void *)&io, (void *)&lq};
-    HIP_OK(hipLaunchKernel(p.row->fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
-    b->lq_ran = true;
+    if (!launch_kernel(b, p, args)) return 0;
+    b->lean[DWBC_LEAN_LINK_QUERY].ran = true;
     return 1;
 }
 
-// why output `what` of the query cannot be named (nullptr: it can)
-static const char *link_query_refusal(const dwbc_batch *b, int what) {
-    if (what < DWBC_LQ_POS || what > DWBC_LQ_JAC) return "link query: unknown output";
-    if (b->lq_n < 1) return "no link query: call dwbc_batch_set_link_query first";
-    if (what == DWBC_LQ_JAC && !b->lq_jac) return "link query: set without Jacobians (dwbc_batch_set_link_query with want_jacobians = 1)";
-    return nullptr;
-}
-
-int dwbc_batch_get_link_query(dwbc_batch *b, int what, void *out, size_t bytes) {
-    if (const char *why = link_query_refusal(b, what)) return fail(why);
-    if (!b->lq_ran) return fail("no link-query output yet: call dwbc_batch_update_kinematics first");
-    const size_t need = dwbc_batch_link_query_bytes(b, what);
-    if (bytes < need) return fail("output buffer too small");
-    HIP_OK(hipSetDevice(b->device));
-    HIP_OK(hipStreamSynchronize(b->stream));
-    return read_back(b, b->buf[fld::kLqPos + what].d, out, need);
-}
-
-int dwbc_batch_bind_link_query(dwbc_batch *b, int what, void *p) {
-    if (const char *why = link_query_refusal(b, what)) return fail(why);
-    HIP_OK(hipSetDevice(b->device));
-    Buf &u = b->buf[fld::kLqPos + what];
-    release(u);
-    b->lq_ran = false;  // (what the batch's own buffer held is not in the new one)
-    if (!p) return ensure(u, dwbc_batch_link_query_bytes(b, what));
-    u.d = p;
-    return 1;
-}
-
-const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b) {
-    static thread_local char name[160];
-    const dwbc_plan::Plan p = link_query_plan(b);
-    if (!p.row) { fail(p.err); return ""; }
-    dwbc_plan::format_name(*p.row, name, sizeof name);
-    return name;
-}
+size_t dwbc_batch_link_query_bytes(const dwbc_batch *b, int what) { return lean_bytes(b, DWBC_LEAN_LINK_QUERY, what); }
+int dwbc_batch_get_link_query(dwbc_batch *b, int what, void *out, size_t bytes) { return lean_get(b, DWBC_LEAN_LINK_QUERY, what, out, bytes); }
+int dwbc_batch_bind_link_query(dwbc_batch *b, int what, void *p) { return lean_bind(b, DWBC_LEAN_LINK_QUERY, what, p); }
+const char *dwbc_batch_link_query_kernel_name(const dwbc_batch *b) { return plan_name(lean_plan(b, DWBC_LEAN_LINK_QUERY), DWBC_LEAN_LINK_QUERY); }
 
 // ---- the dynamics half of UpdateKinematics on its own (A_, A_inv_, B_, G_, CMM_, com_pos): the lean kernel of dwbc_dynamics.h
 static_assert(kDynA == 1u << DWBC_DYN_A && kDynAInv == 1u << DWBC_DYN_A_INV && kDynB == 1u << DWBC_DYN_B && kDynG == 1u << DWBC_DYN_G &&
                   kDynCmm == 1u << DWBC_DYN_CMM && kDynCom == 1u << DWBC_DYN_COM, "DynIO::mask is 1u << dwbc_dynamics_output");
-static dwbc_plan::Plan dynamics_plan(const dwbc_batch *b) {
-    dwbc_plan::Request q = plan_request(b, false);
-    q.dynamics = true;
-    return dwbc_plan::plan(q, b->tables, b->n_tables);
-}
-
-// bytes of all B instances of one output under a request (0: not part of it, no such output)
-static size_t dynamics_bytes(const dwbc_batch *b, unsigned mask, int what) {
-    if (what < DWBC_DYN_A || what > DWBC_DYN_STATUS || !((mask >> what) & 1u)) return 0;
-    const size_t n = (size_t)b->n;
-    const size_t per[7] = {n * n * sizeof(double), n * n * sizeof(double), n * sizeof(double), n * sizeof(double), 6 * n * sizeof(double), 3 * sizeof(double), sizeof(int)};
-    return (size_t)b->B * per[what];
-}
-
-size_t dwbc_batch_dynamics_bytes(const dwbc_batch *b, int what) { return dynamics_bytes(b, b->dyn_mask, what); }
-
-int dwbc_batch_set_dynamics_outputs(dwbc_batch *b, unsigned mask) {
-    constexpr unsigned kAll = (1u << (DWBC_DYN_STATUS + 1)) - 1u;
-    if (mask & ~kAll) return fail("dynamics: unknown output bit (the outputs are 1u << DWBC_DYN_A .. 1u << DWBC_DYN_STATUS)");
-    if (mask) {
-        const dwbc_plan::Plan p = dynamics_plan(b);
-        if (!p.row) return fail(p.err);
-        mask |= 1u << DWBC_DYN_STATUS;
-    }
-    // outputs of the new request, owned by the batch; allocated here, so that dwbc_batch_update_dynamics itself allocates nothing
-    HIP_OK(hipSetDevice(b->device));
-    for (int w = DWBC_DYN_A; w <= DWBC_DYN_STATUS; w++) release(b->buf[fld::kDyA + w]);  // (hipFree waits for the launches that write them)
-    b->dyn_mask = mask;
-    b->dyn_ran = false;
-    for (int w = DWBC_DYN_A; w <= DWBC_DYN_STATUS; w++)
-        if (const size_t bytes = dwbc_batch_dynamics_bytes(b, w))
-            if (!ensure(b->buf[fld::kDyA + w], bytes)) return 0;
-    return 1;
-}
-
 static int launch_dynamics(dwbc_batch *b, const dwbc_plan::Plan &p) {
-    const void *fn = p.row->fn;
-    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        b->lds_attr_set.push_back(fn);
-    }
-    BatchIO io{};  // the state and the model; no buffer of the cycle, the redistribution, the gravity compensation or the link query is named
-    io.B = b->B;
-    io.q = b->dev<double>(fld::kQ);
+    BatchIO io = lean_io(b);  // the state and the model; no buffer of the cycle, the redistribution, the gravity compensation or the link query is named
     io.qdot = b->dev<double>(fld::kQdot);
-    io.body = b->d_body;
-    io.topo = b->d_topo;
-    io.pair_swap_bit = -1;
     DynIO dio{};
-    dio.mask = b->dyn_mask & ~(1u << DWBC_DYN_STATUS);
+    dio.mask = b->lean[DWBC_LEAN_DYNAMICS].mask & ~(1u << DWBC_DYN_STATUS);
     dio.A = b->dev<double>(fld::kDyA);
     dio.A_inv = b->dev<double>(fld::kDyAInv);
     dio.Bv = b->dev<double>(fld::kDyB);
@@ -1251,142 +1172,44 @@ static int launch_dynamics(dwbc_batch *b, const dwbc_plan::Plan &p) {
     dio.com = b->dev<double>(fld::kDyCom);
     dio.status = b->dev<int>(fld::kDyStatus);
     void *args[] = {(void *)&b->su, (void *)&io, (void *)&dio};
-    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
-    b->dyn_ran = true;
+    if (!launch_kernel(b, p, args)) return 0;
+    b->lean[DWBC_LEAN_DYNAMICS].ran = true;
     return 1;
 }
 
 // uploads whatever is pending of the state, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
 static int dynamics_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
-    if (!b->dyn_mask) return fail("no dynamics request: call dwbc_batch_set_dynamics_outputs first");
-    const dwbc_plan::Plan p = dynamics_plan(b);
+    if (!b->lean[DWBC_LEAN_DYNAMICS].mask) return fail(fld::kLean[DWBC_LEAN_DYNAMICS].no_request);
+    const dwbc_plan::Plan p = lean_plan(b, DWBC_LEAN_DYNAMICS);
     if (!p.row) return fail(p.err);
     HIP_OK(hipSetDevice(b->device));
-    bool queued = false;
-    for (const int slot : {fld::kQdot, fld::kQ})
-        if (!send(b, slot, &queued)) return 0;
-    if (queued && !mark_upload(b)) return 0;
+    if (!send_inputs(b, {fld::kQdot, fld::kQ})) return 0;
     if (planned) *planned = p;
     return launch_dynamics(b, p);
 }
 
+int dwbc_batch_set_dynamics_outputs(dwbc_batch *b, unsigned mask) { return lean_set_outputs(b, DWBC_LEAN_DYNAMICS, mask); }
 int dwbc_batch_update_dynamics(dwbc_batch *b) { return dynamics_once(b, nullptr); }
-
 int dwbc_batch_time_dynamics(dwbc_batch *b, int steps, float *ms) {
-    HIP_OK(hipSetDevice(b->device));
     dwbc_plan::Plan p{};
-    if (!dynamics_once(b, &p)) return 0;  // uploads + warm launch
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto timed = [&]() -> int {
-        HIP_OK(hipEventCreate(&e0));
-        HIP_OK(hipEventCreate(&e1));
-        HIP_OK(hipEventRecord(e0, b->stream));
-        for (int i = 0; i < steps; i++)
-            if (!launch_dynamics(b, p)) return 0;
-        HIP_OK(hipEventRecord(e1, b->stream));
-        HIP_OK(hipEventSynchronize(e1));
-        HIP_OK(hipEventElapsedTime(ms, e0, e1));
-        return 1;
-    };
-    const int ok = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return ok;
+    return time_launches(b, steps, ms, [&] { return dynamics_once(b, &p); }, [&] { return launch_dynamics(b, p); });
 }
-
-// why output `what` of the request cannot be named (nullptr: it can)
-static const char *dynamics_refusal(const dwbc_batch *b, int what) {
-    if (what < DWBC_DYN_A || what > DWBC_DYN_STATUS) return "dynamics: unknown output";
-    if (!b->dyn_mask) return "no dynamics request: call dwbc_batch_set_dynamics_outputs first";
-    if (!((b->dyn_mask >> what) & 1u)) return "dynamics: this output was not asked for (dwbc_batch_set_dynamics_outputs)";
-    return nullptr;
-}
-
-int dwbc_batch_get_dynamics(dwbc_batch *b, int what, void *out, size_t bytes) {
-    if (const char *why = dynamics_refusal(b, what)) return fail(why);
-    if (!b->dyn_ran) return fail("no dynamics output yet: call dwbc_batch_update_dynamics first");
-    const size_t need = dwbc_batch_dynamics_bytes(b, what);
-    if (bytes < need) return fail("output buffer too small");
-    HIP_OK(hipSetDevice(b->device));
-    HIP_OK(hipStreamSynchronize(b->stream));
-    return read_back(b, b->buf[fld::kDyA + what].d, out, need);
-}
-
-int dwbc_batch_bind_dynamics(dwbc_batch *b, int what, void *p) {
-    if (const char *why = dynamics_refusal(b, what)) return fail(why);
-    HIP_OK(hipSetDevice(b->device));
-    Buf &u = b->buf[fld::kDyA + what];
-    release(u);
-    b->dyn_ran = false;  // (what the batch's own buffer held is not in the new one)
-    if (!p) return ensure(u, dwbc_batch_dynamics_bytes(b, what));
-    u.d = p;
-    return 1;
-}
-
-const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b) {
-    static thread_local char name[160];
-    const dwbc_plan::Plan p = dynamics_plan(b);
-    if (!p.row) { fail(p.err); return ""; }
-    dwbc_plan::format_name(*p.row, name, sizeof name);
-    return name;
-}
+size_t dwbc_batch_dynamics_bytes(const dwbc_batch *b, int what) { return lean_bytes(b, DWBC_LEAN_DYNAMICS, what); }
+int dwbc_batch_get_dynamics(dwbc_batch *b, int what, void *out, size_t bytes) { return lean_get(b, DWBC_LEAN_DYNAMICS, what, out, bytes); }
+int dwbc_batch_bind_dynamics(dwbc_batch *b, int what, void *p) { return lean_bind(b, DWBC_LEAN_DYNAMICS, what, p); }
+const char *dwbc_batch_dynamics_kernel_name(const dwbc_batch *b) { return plan_name(lean_plan(b, DWBC_LEAN_DYNAMICS), DWBC_LEAN_DYNAMICS); }
 
 // ---- SetContact + CalcContactConstraint on their own (J_C, Lambda_contact, J_C_INV_T, N_C, A_inv_N_C, W, W_inv, NwJw, contact frames):
 // the lean kernel of dwbc_contact_space.h
 static_assert(kCsJC == 1u << DWBC_CS_J_C && kCsLambda == 1u << DWBC_CS_LAMBDA_C && kCsJCInvT == 1u << DWBC_CS_J_C_INV_T && kCsNC == 1u << DWBC_CS_N_C &&
                   kCsAInvNC == 1u << DWBC_CS_A_INV_N_C && kCsW == 1u << DWBC_CS_W && kCsWInv == 1u << DWBC_CS_W_INV && kCsNwJw == 1u << DWBC_CS_NWJW &&
                   kCsPos == 1u << DWBC_CS_CONTACT_POS && kCsRot == 1u << DWBC_CS_CONTACT_ROT, "CsIO::mask is 1u << dwbc_contact_space_output");
-static dwbc_plan::Plan contact_space_plan(const dwbc_batch *b) {
-    dwbc_plan::Request q = plan_request(b, false);
-    q.contact_space = true;
-    return dwbc_plan::plan(q, b->tables, b->n_tables);
-}
-
-// bytes of all B instances of one output under a request (0: not part of it, no such output)
-static size_t contact_space_bytes(const dwbc_batch *b, unsigned mask, int what) {
-    if (what < DWBC_CS_J_C || what > DWBC_CS_STATUS || !((mask >> what) & 1u)) return 0;
-    const size_t n = (size_t)b->n, m = n - 6, d = sizeof(double);
-    const size_t per[11] = {12 * n * d, 144 * d, 12 * n * d, n * n * d, n * n * d, m * m * d, m * m * d, m * 6 * d, 6 * d, 18 * d, sizeof(int)};
-    return (size_t)b->B * per[what];
-}
-
-size_t dwbc_batch_contact_space_bytes(const dwbc_batch *b, int what) { return contact_space_bytes(b, b->cs_mask, what); }
-
-int dwbc_batch_set_contact_space_outputs(dwbc_batch *b, unsigned mask) {
-    constexpr unsigned kAll = (1u << (DWBC_CS_STATUS + 1)) - 1u;
-    if (mask & ~kAll) return fail("contact space: unknown output bit (the outputs are 1u << DWBC_CS_J_C .. 1u << DWBC_CS_STATUS)");
-    if (mask) {
-        const dwbc_plan::Plan p = contact_space_plan(b);
-        if (!p.row) return fail(p.err);
-        mask |= 1u << DWBC_CS_STATUS;
-    }
-    // outputs of the new request, owned by the batch; allocated here, so that dwbc_batch_calc_contact_constraint itself allocates nothing
-    HIP_OK(hipSetDevice(b->device));
-    for (int w = DWBC_CS_J_C; w <= DWBC_CS_STATUS; w++) release(b->buf[fld::kCoJC + w]);  // (hipFree waits for the launches that write them)
-    b->cs_mask = mask;
-    b->cs_ran = false;
-    for (int w = DWBC_CS_J_C; w <= DWBC_CS_STATUS; w++)
-        if (const size_t bytes = dwbc_batch_contact_space_bytes(b, w))
-            if (!ensure(b->buf[fld::kCoJC + w], bytes)) return 0;
-    return 1;
-}
-
 static int launch_contact_space(dwbc_batch *b, const dwbc_plan::Plan &p) {
-    const void *fn = p.row->fn;
-    if (std::find(b->lds_attr_set.begin(), b->lds_attr_set.end(), fn) == b->lds_attr_set.end()) {
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
-        b->lds_attr_set.push_back(fn);
-    }
-    BatchIO io{};  // the state, the flags and the model; no buffer of the cycle or of the other lean launches is named
-    io.B = b->B;
-    io.q = b->dev<double>(fld::kQ);
+    BatchIO io = lean_io(b);  // the state, the flags and the model; no buffer of the cycle or of the other lean launches is named
     io.flags = b->dev<unsigned char>(fld::kFlags);
-    io.body = b->d_body;
-    io.topo = b->d_topo;
     io.hqp = 1;
-    io.pair_swap_bit = -1;
     CsIO cio{};
-    cio.mask = b->cs_mask & ~(1u << DWBC_CS_STATUS);
+    cio.mask = b->lean[DWBC_LEAN_CONTACT_SPACE].mask & ~(1u << DWBC_CS_STATUS);
     cio.J_C = b->dev<double>(fld::kCoJC);
     cio.Lambda_c = b->dev<double>(fld::kCoLambda);
     cio.J_C_INV_T = b->dev<double>(fld::kCoJCInvT);
@@ -1399,85 +1222,33 @@ static int launch_contact_space(dwbc_batch *b, const dwbc_plan::Plan &p) {
     cio.rot = b->dev<double>(fld::kCoRot);
     cio.status = b->dev<int>(fld::kCoStatus);
     void *args[] = {(void *)&b->su, (void *)&io, (void *)&cio};
-    HIP_OK(hipLaunchKernel(fn, dim3(b->B), dim3(p.threads), args, p.lds, b->stream));
-    b->cs_ran = true;
+    if (!launch_kernel(b, p, args)) return 0;
+    b->lean[DWBC_LEAN_CONTACT_SPACE].ran = true;
     return 1;
 }
 
 // uploads whatever is pending of the state and the flags, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+// (the plan's refusals come before the missing request here and after it in dynamics_once: callers see the order, so each family keeps its own)
 static int contact_space_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
-    const dwbc_plan::Plan p = contact_space_plan(b);
+    const dwbc_plan::Plan p = lean_plan(b, DWBC_LEAN_CONTACT_SPACE);
     if (!p.row) return fail(p.err);
-    if (!b->cs_mask) return fail("no contact-space request: call dwbc_batch_set_contact_space_outputs first");
+    if (!b->lean[DWBC_LEAN_CONTACT_SPACE].mask) return fail(fld::kLean[DWBC_LEAN_CONTACT_SPACE].no_request);
     HIP_OK(hipSetDevice(b->device));
-    bool queued = false;
-    for (const int slot : {fld::kQ, fld::kFlags})
-        if (!send(b, slot, &queued)) return 0;
-    if (queued && !mark_upload(b)) return 0;
+    if (!send_inputs(b, {fld::kQ, fld::kFlags})) return 0;
     if (!b->buf[fld::kFlags].d) return fail("no contact flags: call dwbc_batch_set_contact (or bind DWBC_IN_CONTACT) first");
     if (planned) *planned = p;
     return launch_contact_space(b, p);
 }
 
+int dwbc_batch_set_contact_space_outputs(dwbc_batch *b, unsigned mask) { return lean_set_outputs(b, DWBC_LEAN_CONTACT_SPACE, mask); }
 int dwbc_batch_calc_contact_constraint(dwbc_batch *b) { return contact_space_once(b, nullptr); }
-
 int dwbc_batch_time_contact_space(dwbc_batch *b, int steps, float *ms) {
-    HIP_OK(hipSetDevice(b->device));
     dwbc_plan::Plan p{};
-    if (!contact_space_once(b, &p)) return 0;  // uploads + warm launch
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto timed = [&]() -> int {
-        HIP_OK(hipEventCreate(&e0));
-        HIP_OK(hipEventCreate(&e1));
-        HIP_OK(hipEventRecord(e0, b->stream));
-        for (int i = 0; i < steps; i++)
-            if (!launch_contact_space(b, p)) return 0;
-        HIP_OK(hipEventRecord(e1, b->stream));
-        HIP_OK(hipEventSynchronize(e1));
-        HIP_OK(hipEventElapsedTime(ms, e0, e1));
-        return 1;
-    };
-    const int ok = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return ok;
+    return time_launches(b, steps, ms, [&] { return contact_space_once(b, &p); }, [&] { return launch_contact_space(b, p); });
 }
-
-// why output `what` of the request cannot be named (nullptr: it can)
-static const char *contact_space_refusal(const dwbc_batch *b, int what) {
-    if (what < DWBC_CS_J_C || what > DWBC_CS_STATUS) return "contact space: unknown output";
-    if (!b->cs_mask) return "no contact-space request: call dwbc_batch_set_contact_space_outputs first";
-    if (!((b->cs_mask >> what) & 1u)) return "contact space: this output was not asked for (dwbc_batch_set_contact_space_outputs)";
-    return nullptr;
-}
-
-int dwbc_batch_get_contact_space(dwbc_batch *b, int what, void *out, size_t bytes) {
-    if (const char *why = contact_space_refusal(b, what)) return fail(why);
-    if (!b->cs_ran) return fail("no contact-space output yet: call dwbc_batch_calc_contact_constraint first");
-    const size_t need = dwbc_batch_contact_space_bytes(b, what);
-    if (bytes < need) return fail("output buffer too small");
-    HIP_OK(hipSetDevice(b->device));
-    HIP_OK(hipStreamSynchronize(b->stream));
-    return read_back(b, b->buf[fld::kCoJC + what].d, out, need);
-}
-
-int dwbc_batch_bind_contact_space(dwbc_batch *b, int what, void *p) {
-    if (const char *why = contact_space_refusal(b, what)) return fail(why);
-    HIP_OK(hipSetDevice(b->device));
-    Buf &u = b->buf[fld::kCoJC + what];
-    release(u);
-    b->cs_ran = false;  // (what the batch's own buffer held is not in the new one)
-    if (!p) return ensure(u, dwbc_batch_contact_space_bytes(b, what));
-    u.d = p;
-    return 1;
-}
-
-const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b) {
-    static thread_local char name[160];
-    const dwbc_plan::Plan p = contact_space_plan(b);
-    if (!p.row) { fail(p.err); return ""; }
-    dwbc_plan::format_name(*p.row, name, sizeof name);
-    return name;
-}
+size_t dwbc_batch_contact_space_bytes(const dwbc_batch *b, int what) { return lean_bytes(b, DWBC_LEAN_CONTACT_SPACE, what); }
+int dwbc_batch_get_contact_space(dwbc_batch *b, int what, void *out, size_t bytes) { return lean_get(b, DWBC_LEAN_CONTACT_SPACE, what, out, bytes); }
+int dwbc_batch_bind_contact_space(dwbc_batch *b, int what, void *p) { return lean_bind(b, DWBC_LEAN_CONTACT_SPACE, what, p); }
+const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b) { return plan_name(lean_plan(b, DWBC_LEAN_CONTACT_SPACE), DWBC_LEAN_CONTACT_SPACE); }
 
 }  // extern "C"

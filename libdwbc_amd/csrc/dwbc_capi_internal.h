@@ -87,6 +87,7 @@ struct dwbc_batch {
     T *dev(int slot) const { return static_cast<T *>(buf[slot].d); }
     dwbc_batch() {
         for (int s : {dwbc_fields::kTraj, dwbc_fields::kCtime, dwbc_fields::kCustom}) buf[s].h.pinned = false;
+        lean[DWBC_LEAN_GRAV].mask = dwbc_fields::kLean[DWBC_LEAN_GRAV].all();
     }
     double *d_dump = nullptr, *d_body = nullptr;
     int *d_topo = nullptr;
@@ -120,19 +121,16 @@ struct dwbc_batch {
     bool upload_pending = false;
     int n_cu = 0;  // compute units of the batch's device
     bool tau_in_set = false;  // dwbc_batch_redistribute has a torque input: set through the mirror (created with the batch) or bound
-    // the link query (dwbc_batch_set_link_query): entries, whether Jacobians are written, and whether a launch has filled the outputs
+    // per lean launch (enum dwbc_lean_family): the request -- bit i set: output i of the family (dwbc_fields::kLean) is written, 0: none --
+    // and whether a launch has filled the outputs.  Gravity compensation always writes all three; the link query pos | rot | vel, and jac
+    // when it was set with Jacobians; the other two what dwbc_batch_set_*_outputs named, with the status
+    struct {
+        unsigned mask = 0;
+        bool ran = false;
+    } lean[dwbc_fields::kLeanCount];
+    // the entries of the link query (dwbc_batch_set_link_query)
     int lq_n = 0, lq_link[16] = {};
     double lq_point[16][3] = {};
-    bool lq_jac = false, lq_ran = false;
-    bool gv_ran = false;  // a gravity-compensation launch (alone or ahead of a redistribution) has filled the DWBC_GRAV_* outputs
-    // the dynamics request (dwbc_batch_set_dynamics_outputs): bits 1u << dwbc_dynamics_output with DWBC_DYN_STATUS set (0: none), and
-    // whether a launch has filled the outputs
-    unsigned dyn_mask = 0;
-    bool dyn_ran = false;
-    // the contact-space request (dwbc_batch_set_contact_space_outputs): bits 1u << dwbc_contact_space_output with DWBC_CS_STATUS set
-    // (0: none), and whether a launch has filled the outputs
-    unsigned cs_mask = 0;
-    bool cs_ran = false;
     dwbc::DumpLayout dl{};
 };
 

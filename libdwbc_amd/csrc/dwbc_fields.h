@@ -1,7 +1,8 @@
 // dwbc_fields.h -- the data fields of the C-ABI (enum dwbc_field, include/dwbc_batch.h): one row per field with its name, element type,
 // per-instance shape and where it lives.  Host only, no HIP header: dwbc_capi.hip derives dwbc_batch_field_bytes / get / bind_device /
 // host_ptr and dwbc_field_describe from the rows, the Python layer and the facade read them through those entry points, and
-// tests/test_field_table.py pins them.  A new field is one enumerator and one row.
+// tests/test_field_table.py pins them.  A new field is one enumerator and one row.  A second table, at the end, does the same for the
+// outputs of the lean launches.
 #pragma once
 #include <cstddef>
 
@@ -12,21 +13,14 @@ namespace dwbc_fields {
 using namespace dwbc;
 
 // device buffers of a batch that are owned or bound, sized once and uploaded from a host mirror if they have one: the bindable fields,
-// the diagnostics record, and the inputs that are no field -- the task-reference inputs and the per-instance parameter record
-// and the four outputs of a link query, the three of a gravity compensation the seven of a dynamics launch and the eleven of a contact-space launch, which are no field either (dwbc_batch::buf is indexed by this)
+// the diagnostics record, the inputs that are no field (the task-reference inputs and the per-instance parameter record), and the outputs of
+// the lean launches, which are no field either: the table at the end of this file describes them (dwbc_batch::buf is indexed by this)
 enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kInstPar,
             kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kDyA, kDyAInv, kDyB, kDyG, kDyCmm, kDyCom, kDyStatus,
             kCoJC, kCoLambda, kCoJCInvT, kCoNC, kCoAInvNC, kCoW, kCoWInv, kCoNwJw, kCoPos, kCoRot, kCoStatus, kSlotCount };
-static_assert(kCoLambda == kCoJC + DWBC_CS_LAMBDA_C && kCoJCInvT == kCoJC + DWBC_CS_J_C_INV_T && kCoNC == kCoJC + DWBC_CS_N_C && kCoAInvNC == kCoJC + DWBC_CS_A_INV_N_C &&
-                  kCoW == kCoJC + DWBC_CS_W && kCoWInv == kCoJC + DWBC_CS_W_INV && kCoNwJw == kCoJC + DWBC_CS_NWJW && kCoPos == kCoJC + DWBC_CS_CONTACT_POS &&
-                  kCoRot == kCoJC + DWBC_CS_CONTACT_ROT && kCoStatus == kCoJC + DWBC_CS_STATUS, "kCoJC + dwbc_contact_space_output");
-static_assert(kDyAInv == kDyA + DWBC_DYN_A_INV && kDyB == kDyA + DWBC_DYN_B && kDyG == kDyA + DWBC_DYN_G && kDyCmm == kDyA + DWBC_DYN_CMM &&
-                  kDyCom == kDyA + DWBC_DYN_COM && kDyStatus == kDyA + DWBC_DYN_STATUS, "kDyA + dwbc_dynamics_output");
-static_assert(kGvWrench == kGvTau + DWBC_GRAV_WRENCH && kGvStatus == kGvTau + DWBC_GRAV_STATUS, "kGvTau + dwbc_grav_output");
-static_assert(kLqRot == kLqPos + DWBC_LQ_ROT && kLqVel == kLqPos + DWBC_LQ_VEL && kLqJac == kLqPos + DWBC_LQ_JAC, "kLqPos + dwbc_link_query_output");
 
 // one extent of a shape: mul * var + add
-enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal };
+enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal, kQueried };
 struct Dim {
     int mul, var, add;
 };
@@ -125,15 +119,108 @@ inline const Row *find(int id) {
         if (r.id == id) return &r;
     return nullptr;
 }
-inline int extent(const Dim &d, const dwbc_field_dims &s) {
-    const int v[] = {1, s.n, s.n - 6, s.n - 12, s.n_contacts, s.fstar_total, s.max_active, d.var == kDumpTotal ? DumpLayout::make(s.n).total : 0};
+// n_queried: entries of the link query (dwbc_field_dims is ABI and has no place for it; no field depends on it)
+inline int extent(const Dim &d, const dwbc_field_dims &s, int n_queried = 0) {
+    const int v[] = {1, s.n, s.n - 6, s.n - 12, s.n_contacts, s.fstar_total, s.max_active, d.var == kDumpTotal ? DumpLayout::make(s.n).total : 0, n_queried};
     return d.mul * v[d.var] + d.add;
 }
-inline size_t elements(const Row &r, const dwbc_field_dims &s) {  // per instance
+inline size_t elements(const Shape &shape, const dwbc_field_dims &s, int n_queried = 0) {  // per instance
     size_t n = 1;
-    for (int i = 0; i < r.shape.rank; i++) n *= (size_t)extent(r.shape.dim[i], s);
+    for (int i = 0; i < shape.rank; i++) n *= (size_t)extent(shape.dim[i], s, n_queried);
     return n;
 }
 inline size_t item_size(int type) { return type == DWBC_ELEM_F64 ? sizeof(double) : type == DWBC_ELEM_I32 ? sizeof(int) : 1; }
+// what dwbc_field_describe and dwbc_lean_output_describe answer for a row of either table
+inline dwbc_field_info describe(int id, const char *name, int type, const Shape &shape, const dwbc_field_dims &s, int n_queried, bool bindable, bool mirror) {
+    dwbc_field_info o{id, name, type, shape.rank, {1, 1, 1}, elements(shape, s, n_queried) * item_size(type), bindable, mirror};
+    for (int i = 0; i < shape.rank; i++) o.dims[i] = extent(shape.dim[i], s, n_queried);
+    return o;
+}
+
+// ---- the outputs of the lean launches (enum dwbc_lean_family): per family one block with a row per output of its enum, in enumerator
+// order, and the messages of its refusals.  Output i of a family lives in slot rows[0].slot + i, is part of a request when bit i of the
+// family's mask (dwbc_batch::lean) is set, and is sized by its shape: dwbc_capi.hip derives *_bytes / get_* / bind_* and the allocation
+// of a request from the rows, the Python layer reads them through dwbc_lean_output_describe, and tests/test_lean_output_table.py pins them.
+// A new lean launch is one block here and one launch function there.
+struct LeanRow {
+    int id, slot;  // the output's enumerator and its Slot
+    const char *name;  // as libdwbc_amd.Batch spells it
+    int type;
+    Shape shape;  // per instance
+};
+struct Family {
+    const LeanRow *rows;
+    int count;
+    int status;  // index of the status output, which every request implies (-1: none)
+    // refusals (nullptr: the family has no such case): no such output; an unknown bit in a request; nothing requested; the output is not
+    // part of the request; no launch has filled the outputs yet
+    const char *unknown, *unknown_bit, *no_request, *not_asked, *not_run;
+    constexpr unsigned all() const { return (1u << count) - 1u; }
+};
+template <int N>
+constexpr Family family(const LeanRow (&rows)[N], int status, const char *unknown, const char *unknown_bit, const char *no_request, const char *not_asked, const char *not_run) {
+    return {rows, N, status, unknown, unknown_bit, no_request, not_asked, not_run};
+}
+constexpr Dim Q{1, kQueried, 0};  // entries of the link query
+constexpr int F64 = DWBC_ELEM_F64, I32 = DWBC_ELEM_I32;
+
+inline constexpr LeanRow kGravRows[] = {
+    {DWBC_GRAV_TAU, kGvTau, "tau", F64, sh(M)},
+    {DWBC_GRAV_WRENCH, kGvWrench, "wrench", F64, sh(c(12))},
+    {DWBC_GRAV_STATUS, kGvStatus, "status", I32, sh()},
+};
+inline constexpr LeanRow kLinkQueryRows[] = {
+    {DWBC_LQ_POS, kLqPos, "pos", F64, sh(Q, c(3))},
+    {DWBC_LQ_ROT, kLqRot, "rot", F64, sh(Q, c(3), c(3))},
+    {DWBC_LQ_VEL, kLqVel, "vel", F64, sh(Q, c(6))},
+    {DWBC_LQ_JAC, kLqJac, "jac", F64, sh(Q, c(6), N)},  // part of the request only when the query asks for Jacobians
+};
+inline constexpr LeanRow kDynamicsRows[] = {
+    {DWBC_DYN_A, kDyA, "A", F64, sh(N, N)},
+    {DWBC_DYN_A_INV, kDyAInv, "A_inv", F64, sh(N, N)},
+    {DWBC_DYN_B, kDyB, "B", F64, sh(N)},
+    {DWBC_DYN_G, kDyG, "G", F64, sh(N)},
+    {DWBC_DYN_CMM, kDyCmm, "CMM", F64, sh(c(6), N)},
+    {DWBC_DYN_COM, kDyCom, "com", F64, sh(c(3))},
+    {DWBC_DYN_STATUS, kDyStatus, "status", I32, sh()},
+};
+inline constexpr LeanRow kContactSpaceRows[] = {
+    {DWBC_CS_J_C, kCoJC, "J_C", F64, sh(c(12), N)},
+    {DWBC_CS_LAMBDA_C, kCoLambda, "Lambda_c", F64, sh(c(12), c(12))},
+    {DWBC_CS_J_C_INV_T, kCoJCInvT, "J_C_INV_T", F64, sh(c(12), N)},
+    {DWBC_CS_N_C, kCoNC, "N_C", F64, sh(N, N)},
+    {DWBC_CS_A_INV_N_C, kCoAInvNC, "A_inv_N_C", F64, sh(N, N)},
+    {DWBC_CS_W, kCoW, "W", F64, sh(M, M)},
+    {DWBC_CS_W_INV, kCoWInv, "W_inv", F64, sh(M, M)},
+    {DWBC_CS_NWJW, kCoNwJw, "NwJw", F64, sh(M, c(6))},
+    {DWBC_CS_CONTACT_POS, kCoPos, "contact_pos", F64, sh(c(2), c(3))},
+    {DWBC_CS_CONTACT_ROT, kCoRot, "contact_rot", F64, sh(c(2), c(3), c(3))},
+    {DWBC_CS_STATUS, kCoStatus, "status", I32, sh()},
+};
+// indexed by enum dwbc_lean_family
+inline constexpr Family kLean[] = {
+    family(kGravRows, DWBC_GRAV_STATUS, "gravity compensation: unknown output", nullptr, nullptr, nullptr,
+           "no gravity-compensation output yet: call dwbc_batch_grav_compensation (or dwbc_batch_redistribute with DWBC_REDIST_ADD_GRAVITY) first"),
+    family(kLinkQueryRows, -1, "link query: unknown output", nullptr, "no link query: call dwbc_batch_set_link_query first",
+           "link query: set without Jacobians (dwbc_batch_set_link_query with want_jacobians = 1)", "no link-query output yet: call dwbc_batch_update_kinematics first"),
+    family(kDynamicsRows, DWBC_DYN_STATUS, "dynamics: unknown output", "dynamics: unknown output bit (the outputs are 1u << DWBC_DYN_A .. 1u << DWBC_DYN_STATUS)",
+           "no dynamics request: call dwbc_batch_set_dynamics_outputs first", "dynamics: this output was not asked for (dwbc_batch_set_dynamics_outputs)",
+           "no dynamics output yet: call dwbc_batch_update_dynamics first"),
+    family(kContactSpaceRows, DWBC_CS_STATUS, "contact space: unknown output",
+           "contact space: unknown output bit (the outputs are 1u << DWBC_CS_J_C .. 1u << DWBC_CS_STATUS)",
+           "no contact-space request: call dwbc_batch_set_contact_space_outputs first",
+           "contact space: this output was not asked for (dwbc_batch_set_contact_space_outputs)",
+           "no contact-space output yet: call dwbc_batch_calc_contact_constraint first"),
+};
+constexpr int kLeanCount = (int)(sizeof(kLean) / sizeof(kLean[0]));
+constexpr bool lean_rows_in_order() {
+    for (const Family &f : kLean)
+        for (int i = 0; i < f.count; i++)
+            if (f.rows[i].id != i || f.rows[i].slot != f.rows[0].slot + i) return false;
+    return true;
+}
+static_assert(lean_rows_in_order(), "row i of a lean family is enumerator i of its output enum and lives in slot rows[0].slot + i");
+static_assert(kLean[DWBC_LEAN_GRAV].rows == kGravRows && kLean[DWBC_LEAN_LINK_QUERY].rows == kLinkQueryRows && kLean[DWBC_LEAN_DYNAMICS].rows == kDynamicsRows &&
+                  kLean[DWBC_LEAN_CONTACT_SPACE].rows == kContactSpaceRows && kLeanCount == 4,"kLean is indexed by dwbc_lean_family");
 
 }  // namespace dwbc_fields
