@@ -444,6 +444,48 @@ const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b);
 /* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
 int dwbc_batch_time_contact_space(dwbc_batch *b, int steps, float *ms);
 
+/* ---- SetTaskSpace + CalcTaskSpace as a call of its own (reference src/dwbc.cpp:795-816, src/task.cpp:90-93,202-211,
+ * src/wbd.cpp:207-261): what a caller reads off ts_[i] between CalcTaskSpace and a torque law of its own (the reference's harnesses:
+ * Null_task_[i-1] J_kt_ Lambda_task_ f_star_ in tests/sp_test/redu_dyn_test.cpp) in one lean kernel: the contact-space launch's front and,
+ * per task level, the matrices of the restatement's level loop.  No f*, no trajectory, no QP.  The caller asks for a set of outputs; what is
+ * not asked for is not computed: only J_TASK -- nothing behind the kinematics; neither J_KT nor NULL_TASK -- nothing behind Lambda_task; no
+ * NULL_TASK -- no projector, no m x m store.  Outputs per level (buffer slots of their own, no dwbc_field and no output of a
+ * dwbc_lean_family; batch-major; t = dwbc_batch_task_dof(b, level), m = n - 6):
+ *   DWBC_TS_J_TASK (t, n) f64        ts_[level].J_task_
+ *   DWBC_TS_LAMBDA_TASK (t, t) f64   ts_[level].Lambda_task_
+ *   DWBC_TS_J_KT (m, t) f64          ts_[level].J_kt_
+ *   DWBC_TS_NULL_TASK (m, m) f64     ts_[level].Null_task_     every level but the last (the reference forms none there, src/dwbc.cpp:804)
+ *   DWBC_TS_STATUS (1) i32           one per instance, whatever `level` is; always written
+ * Status 0 -- more flags set than two (device-resident flags), a failed Lambda_c, a bad pivot of the W sweep, or a t x t block of some
+ * level that the small inverses reject -- and every asked-for output of that instance is zero.  No active contact is served.
+ * The launch reads the state, the model, the registered contacts, the flags and the task levels, and names no buffer of dwbc_batch_solve
+ * or of the other lean launches.  dwbc_batch_add_task / _add_custom_task / _clear_tasks drop the request (the shapes follow the levels).
+ * Refused (dwbc_last_error), in this order, before anything is launched: DWBC_F32 batches; dwbc_batch_set_max_active_contacts above 2; a
+ * level of more than 6 dof; a TASK_CUSTOM level; a model without the kernel (built in for TOCABI's size on its own tree and on any; every
+ * kernel pack carries its size's); a batch without a task level -- all six at dwbc_batch_set_task_space_outputs already.  Further: an
+ * unknown bit; a launch without a request; get / bind of an output that was not asked for, of a level that does not exist, or of
+ * NULL_TASK of the last level; a get before the first launch of the request; a wrong byte count.
+ * Not built: three contacts, fp32, TASK_CUSTOM levels, levels wider than 6 dof, f* and trajectories (the cycle keeps UpdateTaskSpace);
+ * the facade include/dwbc_amd.hpp keeps serving ts_[i] from its cycle. */
+enum dwbc_task_space_output { DWBC_TS_J_TASK = 0, DWBC_TS_LAMBDA_TASK = 1, DWBC_TS_J_KT = 2, DWBC_TS_NULL_TASK = 3, DWBC_TS_STATUS = 4 };
+/* output `index` of the launch for a model of n dof and a level of t task dof, as dwbc_lean_output_describe answers for the families;
+ * 0 when index is past the end.  Needs no device and no batch. */
+int dwbc_task_space_output_describe(int index, int n, int t, dwbc_field_info *out);
+/* mask: bits 1u << dwbc_task_space_output; DWBC_TS_STATUS is implied.  0 drops the request and its buffers.  Plans at once and allocates
+ * every output of every level, so that the launch allocates nothing; bound buffers are let go of (bind again), earlier results are gone. */
+int dwbc_batch_set_task_space_outputs(dwbc_batch *b, unsigned mask);
+/* one launch, asynchronous on the batch's stream; uploads newer host mirrors of q and the contact flags first, like a solve */
+int dwbc_batch_calc_task_space(dwbc_batch *b);
+size_t dwbc_batch_task_space_bytes(const dwbc_batch *b, int level, int what);  /* of all B instances; 0: not asked for, no such output */
+/* synchronises the stream; bytes must be dwbc_batch_task_space_bytes(b, level, what) */
+int dwbc_batch_get_task_space(dwbc_batch *b, int level, int what, void *host_out, size_t bytes);
+/* zero-copy: a caller-owned DEVICE buffer of dwbc_batch_task_space_bytes(b, level, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_task_space(dwbc_batch *b, int level, int what, void *device_ptr);
+/* name of the kernel dwbc_batch_calc_task_space launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_task_space_kernel_name(const dwbc_batch *b);
+/* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_task_space(dwbc_batch *b, int steps, float *ms);
+
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least
  * squares), optional cost 1/2 y^T H y; levels are solved in sequence inside the null space of the earlier equalities.  The

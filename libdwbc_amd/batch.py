@@ -64,6 +64,19 @@ GRAV_OUTPUTS, LINK_QUERY_OUTPUTS, DYNAMICS_OUTPUTS, CONTACT_SPACE_OUTPUTS = _LEA
 _GRAV, _LINK_QUERY, _DYNAMICS, _CONTACT_SPACE = range(4)
 
 
+def describe_task_space(index, n, t):
+    """output `index` of the task-space launch (same file) for a model of n dof and a level of t task dof, None past the end"""
+    info = _lib.FieldInfo()
+    return info if _lib.load().dwbc_task_space_output_describe(index, n, t, C.byref(info)) else None
+
+
+# name -> enumerator of enum dwbc_task_space_output: no lean family (every output but the status exists once per task level), read from
+# the library once
+TASK_SPACE_OUTPUTS = {}
+while (_r := describe_task_space(len(TASK_SPACE_OUTPUTS), 0, 0)) is not None:
+    TASK_SPACE_OUTPUTS[_r.name.decode()] = _r.id
+
+
 class DwbcError(RuntimeError):
     pass
 
@@ -218,6 +231,7 @@ class Batch:
         makes it 12 dof wide: the batch then runs the general-contact kernel, which takes link and COM levels alike."""
         p = np.ascontiguousarray(point, np.float64)
         _check(self._L.dwbc_batch_add_task(self._h, int(level), int(mode), int(link), p.ctypes.data))
+        self._drop_task_space_tensors()  # (the library dropped the task-space request: its shapes follow the levels)
 
     def set_torque_limit(self, lim):
         if lim is None:
@@ -295,6 +309,7 @@ class Batch:
     def add_custom_task(self, level, task_dof):
         """AddTaskSpace(heirarchy, TASK_CUSTOM, task_dof) (reference include/dwbc.h:318)"""
         _check(self._L.dwbc_batch_add_custom_task(self._h, int(level), int(task_dof)))
+        self._drop_task_space_tensors()
 
     def set_custom_task(self, level, fstar, J):
         """SetTaskSpace(heirarchy, f*, J_task) (reference include/dwbc.h:333): fstar (B, t), J (B, t, n)"""
@@ -328,6 +343,7 @@ class Batch:
     def copy_kinematics_to(self, target):
         """RobotData::CopyKinematicsData(target) (reference include/dwbc.h:375)"""
         _check(self._L.dwbc_batch_copy_kinematics(target._h, self._h))
+        target._drop_task_space_tensors()  # (the task levels came with the set-up: the library dropped the target's task-space request)
         target.n_contacts = self.n_contacts
         target._contact_consts = list(self._contact_consts)
         target._tau_lim = None if self._tau_lim is None else self._tau_lim.copy()
@@ -593,6 +609,73 @@ class Batch:
 
     def time_contact_space(self, steps):
         return self._time("contact_space", steps)
+
+    # ---- SetTaskSpace + CalcTaskSpace on their own: ts_[i].J_task_ / Lambda_task_ / J_kt_ / Null_task_ (reference src/dwbc.cpp:795-816, src/wbd.cpp:207-261)
+    def set_task_space_outputs(self, names):
+        """The outputs calc_task_space() writes per task level of t dof: any of "J_task" (t, n), "Lambda_task" (t, t), "J_kt" (m, t) and
+        "Null_task" (m, m; every level but the last); "status" is always written.  What is not asked for is not computed: only "J_task",
+        nothing behind the kinematics; neither "J_kt" nor "Null_task", nothing behind Lambda_task; no "Null_task", no projector.  An empty
+        list drops the request and its buffers, and so does every change of the task levels.  A new request has new output buffers: bind
+        tensors after it."""
+        mask = 0
+        for k in names:
+            mask |= 1 << TASK_SPACE_OUTPUTS[k]
+        _check(self._L.dwbc_batch_set_task_space_outputs(self._h, mask))
+        self._drop_task_space_tensors()
+
+    def _drop_task_space_tensors(self):
+        for k in [k for k in self._keep if k.startswith("task_space_")]:
+            del self._keep[k]
+
+    def calc_task_space(self):
+        """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA, the contact stage and, per task level, what the request
+        asks for, from the state and the contact flags.  Reads no f*, and leaves every output of solve() and of the other lean launches as
+        it is; they may be called in any order."""
+        _check(self._L.dwbc_batch_calc_task_space(self._h))
+
+    def _task_space_get(self, level, name):
+        what = TASK_SPACE_OUTPUTS[name]
+        r = describe_task_space(what, self.n, self.task_dof(level) if name != "status" else 0)
+        a = np.zeros((self.B,) + tuple(r.dims[: r.rank]), _DTYPES[r.dtype])
+        _check(self._L.dwbc_batch_get_task_space(self._h, int(level), what, a.ctypes.data, a.nbytes))
+        return a
+
+    def task_space(self, level=None):
+        """The asked-for outputs of the last calc_task_space(); synchronises the stream.  ``level`` given: a dict name -> (B, ...) array of
+        that level.  None: ``(levels, status)``, a list of such dicts, one per level, and the status (B,) int32 (0: that instance's
+        outputs are zero)."""
+        status = self._task_space_get(0, "status")  # (refused without a request or before the first launch: nothing else is asked then)
+
+        def one(l):
+            return {k: self._task_space_get(l, k) for k, w in TASK_SPACE_OUTPUTS.items()
+                    if k != "status" and self._L.dwbc_batch_task_space_bytes(self._h, l, w)}
+
+        if level is not None:
+            return one(int(level))
+        n_levels = 0
+        while self.task_dof(n_levels) > 0:  # (0 past the last level)
+            n_levels += 1
+        return [one(l) for l in range(n_levels)], status
+
+    def bind_task_space(self, level, name, tensor):
+        """asked-for output ``name`` of ``level`` into a caller-owned device tensor (float64; "status": int32), written in place by every
+        later launch; None: back to a buffer of the batch's own"""
+        what, key = TASK_SPACE_OUTPUTS[name], f"task_space_{level}_{name}"
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_task_space(self._h, int(level), what, None))
+            self._keep.pop(key, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        nbytes = self._L.dwbc_batch_task_space_bytes(self._h, int(level), what)
+        assert nbytes == 0 or tensor.numel() * tensor.element_size() == nbytes, (name, tensor.shape, nbytes)
+        _check(self._L.dwbc_batch_bind_task_space(self._h, int(level), what, C.c_void_p(tensor.data_ptr())))
+        self._keep[key] = tensor
+
+    def task_space_kernel_name(self):
+        return self._kernel_name("task_space")
+
+    def time_task_space(self, steps):
+        return self._time("task_space", steps)
 
     def time_solves(self, steps, reduced=False):
         return self._time("solves", steps, SOLVE_HQP | SOLVE_INIT | (SOLVE_REDUCED if reduced else 0))

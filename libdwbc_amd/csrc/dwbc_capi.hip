@@ -19,6 +19,7 @@
 using namespace dwbc;
 
 extern "C" const dwbc_plan::Row *dwbc_f32_rows(int *count);  // launch table of the fp32 build (dwbc_kernels_f32.hip)
+extern "C" const dwbc_plan::Row *dwbc_task_space_rows(int *count);  // the built-in task-space kernels (dwbc_kernels_task_space.hip)
 
 // DWBC_F32 batches: the fp32 kernels (dwbc_kernels_f32.hip) work on the double buffers of the boundary; the model table is
 // converted to float once
@@ -318,6 +319,15 @@ static void drop_instance_params(dwbc_batch *b) {
     u.dirty = false;
 }
 
+// the task-space request and its outputs, owned or bound, are let go of: their shapes follow the task levels
+static void drop_task_space(dwbc_batch *b) {
+    if (!b->ts.mask) return;
+    hipSetDevice(b->device);
+    for (int s = fld::kTsFirst; s <= fld::kTsStatusSlot; s++) release(b->buf[s]);  // (hipFree waits for the launches that write them)
+    b->ts.mask = 0;
+    b->ts.ran = false;
+}
+
 dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype) {
     if (!m || B < 1) { g_err = "bad arguments"; return nullptr; }
     if (dtype != DWBC_F64 && dtype != DWBC_F32) { g_err = "dtype must be DWBC_F64 or DWBC_F32"; return nullptr; }
@@ -341,6 +351,9 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     int n_f32 = 0;
     const dwbc_plan::Row *f32 = dwbc_f32_rows(&n_f32);
     b->tables[b->n_tables++] = dwbc_plan::Table{f32, n_f32};
+    int n_ts = 0;
+    const dwbc_plan::Row *ts = dwbc_task_space_rows(&n_ts);
+    b->tables[b->n_tables++] = dwbc_plan::Table{ts, n_ts};
     for (const bool generic : {false, true}) {
         const dwbc_plan::Table t = pack_lookup(b->n, m->m.nb, clean_parents(m->m), generic);
         if (!t.rows) continue;
@@ -417,6 +430,7 @@ int dwbc_batch_clear_contacts(dwbc_batch *b) {
 int dwbc_batch_add_task(dwbc_batch *b, int level, int mode, int link, const double point[3]) {
     std::string err;
     if (!setup_add_task(b->su, level, mode, link, point, err)) return fail(err);
+    drop_task_space(b);
     b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
     b->buf[fld::kFstar].dirty = true;
     return 1;
@@ -425,6 +439,7 @@ int dwbc_batch_add_task(dwbc_batch *b, int level, int mode, int link, const doub
 int dwbc_batch_add_custom_task(dwbc_batch *b, int level, int task_dof) {
     std::string err;
     if (!setup_add_custom_task(b->su, level, task_dof, err)) return fail(err);
+    drop_task_space(b);
     b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
     b->buf[fld::kFstar].dirty = true;
     b->buf[fld::kCustom].h.assign((size_t)b->B * b->su.n_custom * kMaxTaskDof * b->n * sizeof(double));
@@ -447,6 +462,7 @@ int dwbc_batch_set_custom_task(dwbc_batch *b, int level, const double *fstar, co
 }
 
 int dwbc_batch_clear_tasks(dwbc_batch *b) {
+    drop_task_space(b);
     b->su.n_levels = 0;
     b->su.has_com_task = 0;
     b->su.n_custom = 0;
@@ -1001,6 +1017,7 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     HIP_OK(hipSetDevice(dst->device));
     wait_uploads(dst);  // the target's mirrors are rewritten below
     if (dst->su.n_contacts != src->su.n_contacts) drop_instance_params(dst);  // (never copied; the target's own goes with its stride)
+    drop_task_space(dst);  // (the task levels come with the set-up)
     dst->su = src->su;
     Buf &dq = dst->buf[fld::kQ];
     const Buf &sq = src->buf[fld::kQ];
@@ -1250,5 +1267,131 @@ size_t dwbc_batch_contact_space_bytes(const dwbc_batch *b, int what) { return le
 int dwbc_batch_get_contact_space(dwbc_batch *b, int what, void *out, size_t bytes) { return lean_get(b, DWBC_LEAN_CONTACT_SPACE, what, out, bytes); }
 int dwbc_batch_bind_contact_space(dwbc_batch *b, int what, void *p) { return lean_bind(b, DWBC_LEAN_CONTACT_SPACE, what, p); }
 const char *dwbc_batch_contact_space_kernel_name(const dwbc_batch *b) { return plan_name(lean_plan(b, DWBC_LEAN_CONTACT_SPACE), DWBC_LEAN_CONTACT_SPACE); }
+
+// ---- SetTaskSpace + CalcTaskSpace on their own (J_task, Lambda_task, J_kt, Null_task per level): the lean kernel of dwbc_task_space.h.
+// Its outputs are no family of kLean (they exist once per level, in the shape of the level's task dof): the table is dwbc_fields::kTaskSpace,
+// the request and the "ran" flag dwbc_batch::ts, and what follows is the families' plumbing with a level beside the output
+static_assert(kTsJTask == 1u << DWBC_TS_J_TASK && kTsLambda == 1u << DWBC_TS_LAMBDA_TASK && kTsJkt == 1u << DWBC_TS_J_KT && kTsNull == 1u << DWBC_TS_NULL_TASK,
+              "TsIO::mask is 1u << dwbc_task_space_output");
+static dwbc_plan::Plan task_space_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.task_space = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+static int ts_slot(int level, int what) { return what == DWBC_TS_STATUS ? (int)fld::kTsStatusSlot : fld::kTaskSpaceRows[what].slot + level; }
+// levels an output exists on: every one; Null_task all but the last; the status once
+static int ts_levels(const dwbc_batch *b, int what) { return what == DWBC_TS_STATUS ? 1 : b->su.n_levels - (what == DWBC_TS_NULL_TASK ? 1 : 0); }
+
+int dwbc_task_space_output_describe(int index, int n, int t, dwbc_field_info *out) {
+    if (index < 0 || index >= fld::kTaskSpace.count || !out) return 0;
+    const fld::LeanRow &r = fld::kTaskSpaceRows[index];
+    *out = fld::describe(r.id, r.name, r.type, r.shape, dwbc_field_dims{n, 0, 0, 0}, 0, true, false, t);
+    return 1;
+}
+
+size_t dwbc_batch_task_space_bytes(const dwbc_batch *b, int level, int what) {
+    const fld::Family &f = fld::kTaskSpace;
+    if (what < 0 || what >= f.count || !((b->ts.mask >> what) & 1u)) return 0;
+    if (what == DWBC_TS_STATUS) level = 0;
+    if (level < 0 || level >= ts_levels(b, what)) return 0;
+    return (size_t)b->B * fld::elements(f.rows[what].shape, field_dims(b), 0, b->su.t_dof[level]) * fld::item_size(f.rows[what].type);
+}
+
+// why output `what` of `level` cannot be named (nullptr: it can)
+static const char *ts_refusal(const dwbc_batch *b, int level, int what) {
+    const fld::Family &f = fld::kTaskSpace;
+    if (what < 0 || what >= f.count) return f.unknown;
+    if (!b->ts.mask) return f.no_request;
+    if (what != DWBC_TS_STATUS) {
+        if (level < 0 || level >= b->su.n_levels) return "task space: no such task level";
+        if (what == DWBC_TS_NULL_TASK && level == b->su.n_levels - 1) return "task space: the last level has no Null_task (the reference forms none: src/dwbc.cpp:804)";
+    }
+    if (!((b->ts.mask >> what) & 1u)) return f.not_asked;
+    return nullptr;
+}
+
+int dwbc_batch_set_task_space_outputs(dwbc_batch *b, unsigned mask) {
+    const fld::Family &f = fld::kTaskSpace;
+    if (mask & ~f.all()) return fail(f.unknown_bit);
+    if (mask) {
+        const dwbc_plan::Plan p = task_space_plan(b);
+        if (!p.row) return fail(p.err);
+        mask |= 1u << f.status;
+    }
+    drop_task_space(b);  // (hipFree waits for the launches that write them)
+    HIP_OK(hipSetDevice(b->device));
+    b->ts.mask = mask;
+    for (int w = 0; w < f.count; w++)
+        for (int l = 0; l < ts_levels(b, w); l++)
+            if (const size_t bytes = dwbc_batch_task_space_bytes(b, l, w))
+                if (!ensure(b->buf[ts_slot(l, w)], bytes)) return 0;
+    return 1;
+}
+
+int dwbc_batch_get_task_space(dwbc_batch *b, int level, int what, void *out, size_t bytes) {
+    if (const char *why = ts_refusal(b, level, what)) return fail(why);
+    if (!b->ts.ran) return fail(fld::kTaskSpace.not_run);
+    const size_t need = dwbc_batch_task_space_bytes(b, level, what);
+    if (bytes != need) return fail("task space: the host buffer has " + std::to_string(bytes) + " bytes, the output " + std::to_string(need));
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[ts_slot(level, what)].d, out, need);
+}
+
+int dwbc_batch_bind_task_space(dwbc_batch *b, int level, int what, void *p) {
+    if (const char *why = ts_refusal(b, level, what)) return fail(why);
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[ts_slot(level, what)];
+    release(u);
+    b->ts.ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, dwbc_batch_task_space_bytes(b, level, what));
+    u.d = p;
+    return 1;
+}
+
+static int launch_task_space(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    BatchIO io = lean_io(b);  // the state, the flags and the model; no buffer of the cycle or of the other lean launches is named
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.hqp = 1;
+    TsIO tio{};
+    tio.mask = b->ts.mask & ~(1u << DWBC_TS_STATUS);
+    for (int l = 0; l < b->su.n_levels; l++) {
+        tio.J_task[l] = b->dev<double>(ts_slot(l, DWBC_TS_J_TASK));
+        tio.Lambda[l] = b->dev<double>(ts_slot(l, DWBC_TS_LAMBDA_TASK));
+        tio.J_kt[l] = b->dev<double>(ts_slot(l, DWBC_TS_J_KT));
+        tio.Null[l] = b->dev<double>(ts_slot(l, DWBC_TS_NULL_TASK));
+    }
+    tio.status = b->dev<int>(fld::kTsStatusSlot);
+    tio.cs_mask = ts_contact_stage_mask(tio.mask);  // of the contact stage: the columns A^-1 N_c and, where a level reads it, W^+ (cs_out stays NULL)
+    void *args[] = {(void *)&b->su, (void *)&io, (void *)&tio};
+    if (!launch_kernel(b, p, args)) return 0;
+    b->ts.ran = true;
+    return 1;
+}
+
+// uploads whatever is pending of the state and the flags, launches once; *planned (optional): the plan of the launch, for a caller that repeats it
+static int task_space_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
+    const dwbc_plan::Plan p = task_space_plan(b);
+    if (!p.row) return fail(p.err);
+    if (!b->ts.mask) return fail(fld::kTaskSpace.no_request);
+    HIP_OK(hipSetDevice(b->device));
+    if (!send_inputs(b, {fld::kQ, fld::kFlags})) return 0;
+    if (b->su.n_contacts > 0 && !b->buf[fld::kFlags].d) return fail("no contact flags: call dwbc_batch_set_contact (or bind DWBC_IN_CONTACT) first");
+    if (planned) *planned = p;
+    return launch_task_space(b, p);
+}
+
+int dwbc_batch_calc_task_space(dwbc_batch *b) { return task_space_once(b, nullptr); }
+int dwbc_batch_time_task_space(dwbc_batch *b, int steps, float *ms) {
+    dwbc_plan::Plan p{};
+    return time_launches(b, steps, ms, [&] { return task_space_once(b, &p); }, [&] { return launch_task_space(b, p); });
+}
+const char *dwbc_batch_task_space_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = task_space_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
 
 }  // extern "C"

@@ -99,9 +99,9 @@ struct dwbc_batch {
     int warm = 0;           // last solve flags had DWBC_SOLVE_INIT clear
     bool ws_valid = false;  // diag holds the working sets of a full-build launch
     bool last_reduced = false;  // mode of the most recent dwbc_batch_solve (the LQP / JACC entry points need the matching cycle)
-    // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32), then the loaded pack of the
-    // model's own tree, then the generic pack of its size -- resolved once, at creation
-    dwbc_plan::Table tables[4] = {};
+    // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32, the task-space kernels of a translation
+    // unit of their own), then the loaded pack of the model's own tree, then the generic pack of its size -- resolved once, at creation
+    dwbc_plan::Table tables[5] = {};
     int n_tables = 0;
     bool tree_match = false;  // tables[] holds a pack compiled for this model's parent table
     dwbc_plan::Plan last{};   // plan of the last accepted launch (row == nullptr: none yet): kernel_name / launch_info report it
@@ -128,6 +128,12 @@ struct dwbc_batch {
         unsigned mask = 0;
         bool ran = false;
     } lean[dwbc_fields::kLeanCount];
+    // the same for the task-space launch (dwbc_fields::kTaskSpace), whose outputs exist once per task level: what
+    // dwbc_batch_set_task_space_outputs named, with the status; dropped when the task set-up changes
+    struct {
+        unsigned mask = 0;
+        bool ran = false;
+    } ts;
     // the entries of the link query (dwbc_batch_set_link_query)
     int lq_n = 0, lq_link[16] = {};
     double lq_point[16][3] = {};

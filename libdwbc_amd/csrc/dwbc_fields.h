@@ -17,10 +17,12 @@ using namespace dwbc;
 // the lean launches, which are no field either: the table at the end of this file describes them (dwbc_batch::buf is indexed by this)
 enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, kRdWrench, kRdStatus, kDiag, kQdot, kTraj, kCtime, kCustom, kInstPar,
             kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kDyA, kDyAInv, kDyB, kDyG, kDyCmm, kDyCom, kDyStatus,
-            kCoJC, kCoLambda, kCoJCInvT, kCoNC, kCoAInvNC, kCoW, kCoWInv, kCoNwJw, kCoPos, kCoRot, kCoStatus, kSlotCount };
+            kCoJC, kCoLambda, kCoJCInvT, kCoNC, kCoAInvNC, kCoW, kCoWInv, kCoNwJw, kCoPos, kCoRot, kCoStatus,
+            // the task-space launch: output `what` of level l in slot kTsFirst + what * kMaxLevels + l, then the one status
+            kTsFirst, kTsStatusSlot = kTsFirst + 4 * kMaxLevels, kSlotCount };
 
 // one extent of a shape: mul * var + add
-enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal, kQueried };
+enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal, kQueried, kTaskDof };
 struct Dim {
     int mul, var, add;
 };
@@ -119,21 +121,23 @@ inline const Row *find(int id) {
         if (r.id == id) return &r;
     return nullptr;
 }
-// n_queried: entries of the link query (dwbc_field_dims is ABI and has no place for it; no field depends on it)
-inline int extent(const Dim &d, const dwbc_field_dims &s, int n_queried = 0) {
-    const int v[] = {1, s.n, s.n - 6, s.n - 12, s.n_contacts, s.fstar_total, s.max_active, d.var == kDumpTotal ? DumpLayout::make(s.n).total : 0, n_queried};
+// n_queried: entries of the link query; t: task dof of the level a task-space output belongs to (dwbc_field_dims is ABI and has no place
+// for either; no field depends on them)
+inline int extent(const Dim &d, const dwbc_field_dims &s, int n_queried = 0, int t = 0) {
+    const int v[] = {1, s.n, s.n - 6, s.n - 12, s.n_contacts, s.fstar_total, s.max_active, d.var == kDumpTotal ? DumpLayout::make(s.n).total : 0, n_queried, t};
     return d.mul * v[d.var] + d.add;
 }
-inline size_t elements(const Shape &shape, const dwbc_field_dims &s, int n_queried = 0) {  // per instance
+inline size_t elements(const Shape &shape, const dwbc_field_dims &s, int n_queried = 0, int t = 0) {  // per instance
     size_t n = 1;
-    for (int i = 0; i < shape.rank; i++) n *= (size_t)extent(shape.dim[i], s, n_queried);
+    for (int i = 0; i < shape.rank; i++) n *= (size_t)extent(shape.dim[i], s, n_queried, t);
     return n;
 }
 inline size_t item_size(int type) { return type == DWBC_ELEM_F64 ? sizeof(double) : type == DWBC_ELEM_I32 ? sizeof(int) : 1; }
 // what dwbc_field_describe and dwbc_lean_output_describe answer for a row of either table
-inline dwbc_field_info describe(int id, const char *name, int type, const Shape &shape, const dwbc_field_dims &s, int n_queried, bool bindable, bool mirror) {
-    dwbc_field_info o{id, name, type, shape.rank, {1, 1, 1}, elements(shape, s, n_queried) * item_size(type), bindable, mirror};
-    for (int i = 0; i < shape.rank; i++) o.dims[i] = extent(shape.dim[i], s, n_queried);
+inline dwbc_field_info describe(int id, const char *name, int type, const Shape &shape, const dwbc_field_dims &s, int n_queried, bool bindable, bool mirror,
+                                int t = 0) {
+    dwbc_field_info o{id, name, type, shape.rank, {1, 1, 1}, elements(shape, s, n_queried, t) * item_size(type), bindable, mirror};
+    for (int i = 0; i < shape.rank; i++) o.dims[i] = extent(shape.dim[i], s, n_queried, t);
     return o;
 }
 
@@ -222,5 +226,29 @@ constexpr bool lean_rows_in_order() {
 static_assert(lean_rows_in_order(), "row i of a lean family is enumerator i of its output enum and lives in slot rows[0].slot + i");
 static_assert(kLean[DWBC_LEAN_GRAV].rows == kGravRows && kLean[DWBC_LEAN_LINK_QUERY].rows == kLinkQueryRows && kLean[DWBC_LEAN_DYNAMICS].rows == kDynamicsRows &&
                   kLean[DWBC_LEAN_CONTACT_SPACE].rows == kContactSpaceRows && kLeanCount == 4,"kLean is indexed by dwbc_lean_family");
+
+// ---- the outputs of the task-space launch (enum dwbc_task_space_output): no family of kLean -- every output but the status exists once per
+// task level, in the shape of that level's task dof.  Row i is enumerator i; output i of level l lives in slot kTsFirst + i * kMaxLevels + l
+// (the status in kTsStatusSlot) and is part of a request when bit i of dwbc_batch::ts.mask is set.  dwbc_capi.hip derives
+// dwbc_batch_task_space_bytes / get / bind and the allocation of a request from the rows, the Python layer reads them through
+// dwbc_task_space_output_describe.
+constexpr Dim Tt{1, kTaskDof, 0};  // task dof of the level
+inline constexpr LeanRow kTaskSpaceRows[] = {
+    {DWBC_TS_J_TASK, kTsFirst, "J_task", F64, sh(Tt, N)},
+    {DWBC_TS_LAMBDA_TASK, kTsFirst + kMaxLevels, "Lambda_task", F64, sh(Tt, Tt)},
+    {DWBC_TS_J_KT, kTsFirst + 2 * kMaxLevels, "J_kt", F64, sh(M, Tt)},
+    {DWBC_TS_NULL_TASK, kTsFirst + 3 * kMaxLevels, "Null_task", F64, sh(M, M)},
+    {DWBC_TS_STATUS, kTsStatusSlot, "status", I32, sh()},
+};
+inline constexpr Family kTaskSpace =
+    family(kTaskSpaceRows, DWBC_TS_STATUS, "task space: unknown output", "task space: unknown output bit (the outputs are 1u << DWBC_TS_J_TASK .. 1u << DWBC_TS_STATUS)",
+           "no task-space request: call dwbc_batch_set_task_space_outputs first", "task space: this output was not asked for (dwbc_batch_set_task_space_outputs)",
+           "no task-space output yet: call dwbc_batch_calc_task_space first");
+constexpr bool task_space_rows_in_order() {
+    for (int i = 0; i < kTaskSpace.count; i++)
+        if (kTaskSpaceRows[i].id != i || kTaskSpaceRows[i].slot != (i == DWBC_TS_STATUS ? (int)kTsStatusSlot : kTsFirst + i * kMaxLevels)) return false;
+    return true;
+}
+static_assert(task_space_rows_in_order() && kTaskSpace.count == DWBC_TS_STATUS + 1, "row i of the task-space table is enumerator i of dwbc_task_space_output");
 
 }  // namespace dwbc_fields

@@ -14,6 +14,7 @@
 #include "dwbc_link_query.h"
 #include "dwbc_dynamics.h"
 #include "dwbc_contact_space.h"
+#include "dwbc_task_space.h"
 
 namespace dwbc {
 
@@ -148,6 +149,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
     contact_space_instance<N, NB, 64, Topo>(th, su, io, cio, inst, lds);
 }
 
+// SetTaskSpace + CalcTaskSpace in a launch of their own (dwbc_task_space.h): the contact-space kernel's front and, per task level and each
+// behind a wave-uniform branch on TsIO::mask, J_task, Lambda_task, J_kt and Null_task -- LdsTs (38 KB at TOCABI's size: four workgroups per
+// CU), register-capped like the other lean kernels
+template <int N, int NB, class Topo>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_task_space_kernel(const Setup su, const BatchIO io, const TsIO tio) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    task_space_instance<N, NB, 64, Topo>(th, su, io, tio, inst, lds);
+}
+
 #define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
@@ -225,6 +238,13 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_CONTACT_SPACE(N, NB, TOPO, TK) \
     DWBC_ROW(N, NB, 0, TK, kContactSpace, 0u, (LdsCs<N, NB>::total_bytes), kNT, dwbc_contact_space_kernel, N, NB, dwbc::TOPO),
 #endif
+// the task-space kernel: fp64 (DWBC_NO_TASK_SPACE_KERNEL: fp32), for a constant tree or any tree of the size; every kernel pack carries its own
+#ifdef DWBC_NO_TASK_SPACE_KERNEL
+#define DWBC_ROW_TASK_SPACE(N, NB, TOPO, TK)
+#else
+#define DWBC_ROW_TASK_SPACE(N, NB, TOPO, TK) \
+    DWBC_ROW(N, NB, 0, TK, kTaskSpace, 0u, (LdsTs<N, NB>::total_bytes), kNT, dwbc_task_space_kernel, N, NB, dwbc::TOPO),
+#endif
 // instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
 // and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
 // model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
@@ -233,7 +253,7 @@ namespace lp = dwbc_plan;
 #define DWBC_ROWS_TOCABI_ANY(NLV) \
     DWBC_ROW(39, 34, NLV, 0, kCycle, 0u, (Lds2<39, 34, NLV>::total_bytes), kNT, dwbc_cycle_kernel_v2, 39, 34, NLV, DWBC_NT, true, dwbc::TopoGeneric), \
     DWBC_ROW_REDUCED(39, 34, NLV, TopoGeneric, 0)
-#ifndef DWBC_PACK_N
+#if !defined(DWBC_PACK_N) && !defined(DWBC_NO_BUILTIN_ROWS)
 const lp::Row kRows[] = {
 #ifdef DWBC_EXPERIMENT
     // A/B build (make experiment VARIANT=.. XFLAGS=..): only the BASELINE config[1] instantiations, seconds to compile
@@ -251,6 +271,8 @@ const lp::Row kRows[] = {
     DWBC_ROW_CONTACT_SPACE(39, 34, TopoTocabi, 1) DWBC_ROW_CONTACT_SPACE(39, 34, TopoGeneric, 0)
 };
 #endif
+// (the built-in task-space rows are emitted by a translation unit of their own, dwbc_kernels_task_space.hip: the code objects of the kernels
+// above stay the ones they were whatever that kernel grows into)
 
 // what a pack and the library that loads it must agree on (both are built from this header): the sizes of the shared structures
 // and a hash of the kernel sources (Makefile: DWBC_SRC_HASH), so that a pack left over from older kernel code is refused

@@ -8,6 +8,7 @@
 #define DWBC_NO_LINK_QUERY_KERNEL
 #define DWBC_NO_DYNAMICS_KERNEL
 #define DWBC_NO_CONTACT_SPACE_KERNEL
+#define DWBC_NO_TASK_SPACE_KERNEL
 #define dwbc dwbc_f32
 #include "dwbc_kernels.h"
 #undef dwbc

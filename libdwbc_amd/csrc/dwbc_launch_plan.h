@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation, the dynamics of UpdateKinematics or the contact space of CalcContactConstraint):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation, the dynamics of UpdateKinematics, the contact space of CalcContactConstraint or the task space of CalcTaskSpace):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -13,7 +13,8 @@ enum Arith { kDouble = 0, kFloat = 1 };
 // (dwbc_redistribute.h, GRAV = true)
 // the dynamics half of UpdateKinematics on its own (dwbc_dynamics.h)
 // SetContact + CalcContactConstraint on their own (dwbc_contact_space.h)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6, kContactSpace = 7 };
+// SetTaskSpace + CalcTaskSpace on their own (dwbc_task_space.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6, kContactSpace = 7, kTaskSpace = 8 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -76,6 +77,9 @@ struct Request {
     // the model, arith, max_active and n_contacts
     bool contact_space = false;
     int n_contacts = 0;  // registered contacts of the batch (read by the contact-space request alone)
+    // not a cycle either: SetTaskSpace + CalcTaskSpace on their own (dwbc_batch_calc_task_space); of the members above it reads the model,
+    // arith, max_active, levels, wide_tasks and n_custom
+    bool task_space = false;
 };
 
 struct Plan {
@@ -169,6 +173,17 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         const Row *r = Candidates(q, kContactSpace, tabs, n_tabs).pick(0u, 0u);
         if (!r) return refuse("no contact-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         if (q.n_contacts < 1) return refuse("contact space: no contact constraint (call dwbc_batch_add_contact first)");
+        return run(r, false);
+    }
+    // task space of CalcTaskSpace: one kernel per model size and tree, whatever the batch size, hqp, warm or the dump record are
+    if (q.task_space) {
+        if (q.arith == kFloat) return refuse("task space: fp64 batches only");
+        if (q.max_active > 2) return refuse("task space: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
+        if (q.wide_tasks) return refuse("task space: task levels of at most 6 dof");
+        if (q.n_custom > 0) return refuse("task space: TASK_CUSTOM levels are not built (their J_task is the caller's own)");
+        const Row *r = Candidates(q, kTaskSpace, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return refuse("no task-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (q.levels < 1) return refuse("task space: no task level (call dwbc_batch_add_task first)");
         return run(r, false);
     }
     // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the

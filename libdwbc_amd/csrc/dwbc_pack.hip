@@ -3,11 +3,13 @@
 // (`make pack N=.. NB=..`; libdwbc_amd.build_pack(model) from Python).  The reference is model-generic (any URDF RBDL reads:
 // src/dwbc.cpp:140-277, tests/dof_test/*.urdf); here the kernels keep their matrices in registers, so the sizes are template
 // arguments and each (N, NB) is compiled once.  TopoGeneric build (dense A^-1 sweep), fp64, full-model cycle, the redistribution
-// of a caller-supplied torque, gravity compensation, the dynamics of UpdateKinematics and the contact space of CalcContactConstraint; the reduced (centroidal) path is laid out for TOCABI's tree and is not part of a pack.  dwbc_batch_create() dlopens the pack of the
+// of a caller-supplied torque, gravity compensation, the dynamics of UpdateKinematics, the contact space of CalcContactConstraint and the task space of CalcTaskSpace; the reduced (centroidal) path is laid out for TOCABI's tree and is not part of a pack.  dwbc_batch_create() dlopens the pack of the
 // loaded model's size from the directory of libdwbc_hip.so (or $DWBC_PACK_DIR).
 #ifndef DWBC_PACK_N
 #error "compile with -DDWBC_PACK_N=<system dof> -DDWBC_PACK_NB=<bodies>"
 #endif
+#include <vector>
+
 #include "dwbc_kernels.h"
 
 using namespace dwbc;
@@ -48,6 +50,10 @@ static const dwbc_plan::Row kPack[] = {
 // SetContact + CalcContactConstraint on their own (dwbc_contact_space.h)
     DWBC_ROW_CONTACT_SPACE(DWBC_PACK_N, DWBC_PACK_NB, DWBC_PACK_TOPO, DWBC_PACK_KIND)
 };
+// SetTaskSpace + CalcTaskSpace on their own (dwbc_task_space.h): the pack's row comes from a translation unit of its own
+// (dwbc_pack_task_space.hip, linked into the same file), as the built-in ones do -- instantiated beside them it changed the code objects of
+// the pack's cycle, redistribution, gravity-compensation and contact-space kernels
+extern "C" const dwbc_plan::Row *dwbc_pack_task_space_rows(int *count);
 
 #ifdef DWBC_PACK_PARENTS
 // the tree this pack was compiled for: the loader compares it with the model's
@@ -57,7 +63,14 @@ extern "C" const int *dwbc_pack_parents(int *nb) {
 }
 #endif
 extern "C" const dwbc_plan::Row *dwbc_pack_table(int *count, unsigned *abi_tag) {
-    *count = (int)(sizeof(kPack) / sizeof(kPack[0]));
+    static const std::vector<dwbc_plan::Row> all = [] {  // the rows of this translation unit, then the task-space kernel's
+        std::vector<dwbc_plan::Row> v(kPack, kPack + sizeof(kPack) / sizeof(kPack[0]));
+        int n = 0;
+        const dwbc_plan::Row *ts = dwbc_pack_task_space_rows(&n);
+        v.insert(v.end(), ts, ts + n);
+        return v;
+    }();
+    *count = (int)all.size();
     *abi_tag = kernel_abi_tag();
-    return kPack;
+    return all.data();
 }
