@@ -152,6 +152,11 @@ int dwbc_model_link_id(const dwbc_model *m, const char *name); /* case-insensiti
 const char *dwbc_model_link_name(const dwbc_model *m, int link);
 int dwbc_model_get_arrays(const dwbc_model *m, int32_t *parent, double *R_T, double *p_T, double *axis, double *mass,
                           double *com, double *inertia);
+/* The model as the kernels read it: nb records of 25 doubles, one per body in the order of the arrays above,
+ *   [ R_T[9] row-major | p_T[3] | axis[3] | mass | com[3] | Icom xx xy xz yy yz zz ]
+ * (joint frame in the parent's frame, joint axis, then the link's mass, COM offset and inertia about the COM in the link frame; body 0 is the
+ * floating base, whose axis is not read).  `out` is nb x 25.  This is the record of dwbc_batch_set_instance_model, once per instance. */
+int dwbc_model_body_table(const dwbc_model *m, double *out);
 /* ---- init-time model surgery (reference include/dwbc.h:206-226, src/dwbc.cpp:1764-2382, 2707-2730).  Each call returns a NEW
  * model (NULL + dwbc_last_error on refusal) and leaves its argument alone: destroy both when done.  A model of another size
  * runs on its own kernel pack (`make -C libdwbc_amd/csrc pack N=.. NB=..`).
@@ -222,6 +227,25 @@ int dwbc_batch_task_dof(const dwbc_batch *b, int level);
 int dwbc_batch_instance_param_stride(const dwbc_batch *b);
 int dwbc_batch_set_instance_params(dwbc_batch *b, const double *host);
 int dwbc_batch_bind_instance_params(dwbc_batch *b, void *device_ptr);
+/* Per-instance link mass, COM, inertia and joint frames (no counterpart in the reference either): one body table per instance,
+ * dwbc_batch_instance_model_stride(b) = nb * 25 doubles each, in the layout of dwbc_model_body_table.  While a batch has the record,
+ * instance i is computed with table i: the full-model cycle of dwbc_batch_solve on every launch route and the six lean launches
+ * (redistribution, gravity compensation, link query, dynamics, contact space, task space) run the dwbc_im:: build of the kernel they would
+ * run without it (dwbc_batch_kernel_name says so).  The tree, the contact and task set-up stay per batch; the record and the instance
+ * parameters above may be present together.  It is no dwbc_field:
+ *   set   host is B x stride.  Checked per body, the reason in dwbc_last_error: every entry finite, mass > 0, inertia diagonal > 0, and for
+ *         bodies >= 1 |axis| = 1 and R_T R_T^T = I to 1e-6; on failure 0 is returned and the batch keeps what it had.  Uploaded by the next
+ *         launch on the batch's stream from a page-locked copy.  NULL drops the record: the model's own table holds again.  Refused while
+ *         a device buffer is bound.
+ *   bind  a caller-owned DEVICE buffer of B x stride doubles (a torch tensor), read in place by every later launch: no transfer and no
+ *         validation.  NULL unbinds.
+ * Both refuse at once: a DWBC_F32 batch, a model that is not on TOCABI's constant tree (another tree of its size, or a batch created under
+ * DWBC_DENSE_SWEEP) and a kernel-pack model.  dwbc_batch_copy_kinematics does not copy the record.  Refused with a record (nothing is
+ * launched): DWBC_SOLVE_REDUCED, three active contacts or a task level of more than 6 dof (the general-contact kernel),
+ * dwbc_batch_configure_lqp* / dwbc_batch_solve_jacc*.  The C++ facade dwbc_amd.hpp does not expose it. */
+int dwbc_batch_instance_model_stride(const dwbc_batch *b);
+int dwbc_batch_set_instance_model(dwbc_batch *b, const double *host);
+int dwbc_batch_bind_instance_model(dwbc_batch *b, void *device_ptr);
 
 /* UpdateKinematics(q, qdot, qddot) include/dwbc.h:251 : q is B x (ndof+1); qdot (B x ndof) may be NULL: only B_, the link
  * velocities and the on-device task reference read it; qddot is accepted for signature parity and unused */

@@ -146,6 +146,10 @@ SYMBOLS = [
     ("dwbc_batch_instance_param_stride", _i, [_vp]),
     ("dwbc_batch_set_instance_params", _i, [_vp, _vp]),
     ("dwbc_batch_bind_instance_params", _i, [_vp, _vp]),
+    ("dwbc_model_body_table", _i, [_vp, _vp]),
+    ("dwbc_batch_instance_model_stride", _i, [_vp]),
+    ("dwbc_batch_set_instance_model", _i, [_vp, _vp]),
+    ("dwbc_batch_bind_instance_model", _i, [_vp, _vp]),
 ]
 
 _lib = None

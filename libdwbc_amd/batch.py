@@ -190,6 +190,37 @@ class Model:
         out["nb"], out["ndof"] = nb, self.ndof
         return out
 
+    def body_table(self):
+        """the model as the kernels read it, (nb, 25): per body R_T[9] row-major, p_T[3], axis[3], mass, com[3], Icom xx xy xz yy yz zz"""
+        out = np.zeros((self.nb, 25))
+        _check(self._L.dwbc_model_body_table(self._h, out.ctypes.data))
+        return out
+
+    def instance_model(self, B, mass=None, com=None, inertia=None, p_T=None, R_T=None, axis=None):
+        """(B, nb, 25): one body table per instance for Batch.set_instance_model, in the packing of body_table().  mass (B, nb), com
+        (B, nb, 3), inertia (B, nb, 3, 3) about the COM (the upper triangle is read), p_T (B, nb, 3), R_T (B, nb, 3, 3), axis (B, nb, 3);
+        a field left at None is the model's own."""
+        B, nb = int(B), self.nb
+        rec = np.broadcast_to(self.body_table(), (B, nb, 25)).copy()
+
+        def put(x, shape, cols):
+            if x is None:
+                return
+            x = np.asarray(x, np.float64)
+            assert x.shape == (B, nb) + shape, x.shape
+            rec[:, :, cols] = x.reshape(B, nb, -1)
+
+        put(R_T, (3, 3), slice(0, 9))
+        put(p_T, (3,), slice(9, 12))
+        put(axis, (3,), slice(12, 15))
+        put(mass, (), slice(15, 16))
+        put(com, (3,), slice(16, 19))
+        if inertia is not None:
+            I = np.asarray(inertia, np.float64)
+            assert I.shape == (B, nb, 3, 3), I.shape
+            rec[:, :, 19:25] = I.reshape(B, nb, 9)[:, :, [0, 1, 2, 4, 5, 8]]
+        return rec
+
     def __del__(self):
         try:
             if self._h:
@@ -288,6 +319,39 @@ class Batch:
         assert tensor.numel() * tensor.element_size() == self.B * self.instance_param_stride * 8, tensor.shape
         _check(self._L.dwbc_batch_bind_instance_params(self._h, C.c_void_p(tensor.data_ptr())))
         self._keep["instance_params"] = tensor
+
+    # ---- per-instance link mass, COM, inertia and joint frames (domain randomisation of the robot itself: payloads, link lengths)
+    @property
+    def instance_model_shape(self):
+        """shape of the per-instance model record: (B, nb, 25)"""
+        return (self.B, self.model.nb, int(self._L.dwbc_batch_instance_model_stride(self._h)) // self.model.nb)
+
+    def set_instance_model(self, tables):
+        """One body table per instance, (B, nb, 25) as Model.instance_model packs it: while the batch has it, instance i of solve() (every
+        launch route of the full-model cycle) and of the six lean launches is computed with table i.  Checked per body (finite, mass > 0,
+        inertia diagonal > 0, unit axis and orthonormal R_T for bodies >= 1); a refused record leaves the batch as it was.  None drops it.
+        fp64 batches on TOCABI's tree only; refused with a record: solve(reduced=True), three active contacts, task levels of more than
+        6 dof, LQP / JACC."""
+        if tables is None:
+            _check(self._L.dwbc_batch_set_instance_model(self._h, None))
+            return
+        t = np.ascontiguousarray(tables, np.float64)
+        if t.shape != self.instance_model_shape:
+            raise DwbcError(f"instance model: shape {t.shape}, expected {self.instance_model_shape}")
+        _check(self._L.dwbc_batch_set_instance_model(self._h, t.ctypes.data))
+
+    def bind_instance_model(self, tensor):
+        """The record as a caller-owned device tensor of (B, nb, 25) float64, read in place by every later launch (no transfer, no
+        validation); None unbinds"""
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_instance_model(self._h, None))
+            self._keep.pop("instance_model", None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        if tuple(tensor.shape) != self.instance_model_shape or tensor.element_size() != 8:
+            raise DwbcError(f"instance model: tensor of shape {tuple(tensor.shape)}, expected float64 {self.instance_model_shape}")
+        _check(self._L.dwbc_batch_bind_instance_model(self._h, C.c_void_p(tensor.data_ptr())))
+        self._keep["instance_model"] = tensor
 
     @property
     def fstar_size(self):

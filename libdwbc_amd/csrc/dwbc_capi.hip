@@ -20,6 +20,13 @@ using namespace dwbc;
 
 extern "C" const dwbc_plan::Row *dwbc_f32_rows(int *count);  // launch table of the fp32 build (dwbc_kernels_f32.hip)
 extern "C" const dwbc_plan::Row *dwbc_task_space_rows(int *count);  // the built-in task-space kernels (dwbc_kernels_task_space.hip)
+// the kernels that read one body table per instance (dwbc_kernels_im.h), split over translation units of their own
+extern "C" const dwbc_plan::Row *dwbc_im_rows_l1(int *count);
+extern "C" const dwbc_plan::Row *dwbc_im_rows_l2(int *count);
+extern "C" const dwbc_plan::Row *dwbc_im_rows_l3(int *count);
+extern "C" const dwbc_plan::Row *dwbc_im_rows_l4(int *count);
+extern "C" const dwbc_plan::Row *dwbc_im_rows_pair(int *count);
+extern "C" const dwbc_plan::Row *dwbc_im_rows_lean(int *count);
 
 // DWBC_F32 batches: the fp32 kernels (dwbc_kernels_f32.hip) work on the double buffers of the boundary; the model table is
 // converted to float once
@@ -125,6 +132,19 @@ bool has_size(const dwbc_plan::Table &t, int n, int nb) {
 }
 const dwbc_plan::Table kBuiltin{kRows, (int)(sizeof(kRows) / sizeof(kRows[0]))};
 bool builtin_has(int n, int nb) { return has_size(kBuiltin, n, nb); }
+// the rows of the per-instance-model build as one table (the planner takes the rows of a kind from one table)
+dwbc_plan::Table inst_model_table() {
+    static const std::vector<dwbc_plan::Row> rows = [] {
+        std::vector<dwbc_plan::Row> v;
+        for (const auto fn : {dwbc_im_rows_l1, dwbc_im_rows_l2, dwbc_im_rows_l3, dwbc_im_rows_l4, dwbc_im_rows_pair, dwbc_im_rows_lean}) {
+            int n = 0;
+            const dwbc_plan::Row *r = fn(&n);
+            v.insert(v.end(), r, r + n);
+        }
+        return v;
+    }();
+    return dwbc_plan::Table{rows.data(), (int)rows.size()};
+}
 std::vector<int> clean_parents(const Model &m) {
     std::vector<int> p(m.parent.size());
     for (size_t i = 0; i < p.size(); i++) p[i] = m.parent[i] < 0 ? 0 : m.parent[i];
@@ -236,6 +256,7 @@ static dwbc_plan::Request plan_request(const dwbc_batch *b, bool reduced) {
     q.n_custom = b->su.n_custom;
     q.dump_on = b->dump_on;
     q.inst_par = b->buf[dwbc_fields::kInstPar].d || !b->buf[dwbc_fields::kInstPar].h.empty();
+    q.inst_model = b->buf[dwbc_fields::kInstModel].d || !b->buf[dwbc_fields::kInstModel].h.empty();
     q.no_wide = getenv("DWBC_NO_WIDE") != nullptr;
     q.no_pair = getenv("DWBC_NO_PAIR") != nullptr;
     q.no_lean = getenv("DWBC_NO_LEAN") != nullptr;
@@ -319,6 +340,23 @@ static void drop_instance_params(dwbc_batch *b) {
     u.dirty = false;
 }
 
+// the per-instance body tables, owned or bound, are let go of: the model's own table holds for every instance again
+static void drop_instance_model(dwbc_batch *b) {
+    Buf &u = b->buf[fld::kInstModel];
+    if (!u.d && u.h.empty()) return;
+    hipSetDevice(b->device);
+    wait_uploads(b);
+    release(u);  // (hipFree waits for the launches that read it)
+    u.h.clear();
+    u.dirty = false;
+}
+// the body table a launch hands to its kernel: the per-instance record while the batch carries one (the planner then picks a dwbc_im::
+// kernel, which reads table `inst` of it), else the model's
+static const double *launch_body(const dwbc_batch *b) {
+    const double *rec = b->dev<double>(fld::kInstModel);
+    return rec ? rec : b->d_body;
+}
+
 // the task-space request and its outputs, owned or bound, are let go of: their shapes follow the task levels
 static void drop_task_space(dwbc_batch *b) {
     if (!b->ts.mask) return;
@@ -354,6 +392,7 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     int n_ts = 0;
     const dwbc_plan::Row *ts = dwbc_task_space_rows(&n_ts);
     b->tables[b->n_tables++] = dwbc_plan::Table{ts, n_ts};
+    b->tables[b->n_tables++] = inst_model_table();
     for (const bool generic : {false, true}) {
         const dwbc_plan::Table t = pack_lookup(b->n, m->m.nb, clean_parents(m->m), generic);
         if (!t.rows) continue;
@@ -551,6 +590,55 @@ int dwbc_batch_bind_instance_params(dwbc_batch *b, void *p) {
     return 1;
 }
 
+// ---- one body table per instance (mass, COM, inertia and joint frames): B x nb x kBodyStride doubles in the layout of Model::body_table
+int dwbc_batch_instance_model_stride(const dwbc_batch *b) { return b->su.nb * kBodyStride; }
+
+// why this batch cannot carry a record at all (nullptr: it can)
+static const char *instance_model_refusal(const dwbc_batch *b) {
+    if (b->dtype == DWBC_F32) return "per-instance model: fp64 batches only";
+    if (!builtin_has(b->n, b->su.nb)) return "per-instance model: not built for kernel-pack models (TOCABI's size and tree only)";
+    if (b->su.topo_kind != 1) return "per-instance model: built for TOCABI's constant tree only (this model's tree differs, or the batch was created under DWBC_DENSE_SWEEP)";
+    return nullptr;
+}
+
+int dwbc_batch_set_instance_model(dwbc_batch *b, const double *host) {
+    Buf &u = b->buf[fld::kInstModel];
+    if (const char *why = instance_model_refusal(b)) return fail(why);
+    if (u.bound()) return fail("the instance model is bound to a device buffer");
+    if (!host) { drop_instance_model(b); return 1; }
+    const int nb = b->su.nb;
+    for (int i = 0; i < b->B; i++)
+        for (int k = 0; k < nb; k++) {
+            const double *r = host + ((size_t)i * nb + k) * kBodyStride;
+            auto bad = [&](const char *what) { return fail("instance model: instance " + std::to_string(i) + ", body " + std::to_string(k) + ": " + what); };
+            for (int a = 0; a < kBodyStride; a++)
+                if (!std::isfinite(r[a])) return bad("an entry is not finite");
+            if (!(r[BF_MASS] > 0.0)) return bad("mass must be > 0");
+            if (!(r[BF_ICOM] > 0.0) || !(r[BF_ICOM + 3] > 0.0) || !(r[BF_ICOM + 5] > 0.0)) return bad("the diagonal of the inertia must be > 0");
+            if (k == 0) continue;  // (the floating base has no joint)
+            const double *ax = r + BF_AXIS, *R = r + BF_RT;
+            if (std::fabs(std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]) - 1.0) > 1e-6) return bad("the joint axis must have unit length (to 1e-6)");
+            for (int x = 0; x < 3; x++)
+                for (int y = 0; y < 3; y++) {
+                    const double d = R[3 * x] * R[3 * y] + R[3 * x + 1] * R[3 * y + 1] + R[3 * x + 2] * R[3 * y + 2];
+                    if (std::fabs(d - (x == y ? 1.0 : 0.0)) > 1e-6) return bad("R_T must be orthonormal (R_T R_T^T = I to 1e-6)");
+                }
+        }
+    wait_uploads(b);
+    u.h.assign(host, (size_t)b->B * nb * kBodyStride * sizeof(double));
+    u.dirty = true;
+    return 1;
+}
+
+int dwbc_batch_bind_instance_model(dwbc_batch *b, void *p) {
+    Buf &u = b->buf[fld::kInstModel];
+    if (const char *why = instance_model_refusal(b)) return fail(why);
+    if (!p && !u.bound()) return 1;  // nothing bound
+    drop_instance_model(b);
+    u.d = p;
+    return 1;
+}
+
 int dwbc_batch_fstar_size(const dwbc_batch *b) { return b->su.fstar_total; }
 int dwbc_batch_task_dof(const dwbc_batch *b, int level) { return (level >= 0 && level < b->su.n_levels) ? b->su.t_dof[level] : 0; }
 
@@ -605,6 +693,7 @@ int dwbc_batch_set_max_active_contacts(dwbc_batch *b, int n) {
     if (n > 2) {
         if (b->dtype == DWBC_F32) return fail("three active contacts: fp64 batches only");
         const dwbc_plan::Request q = plan_request(b, false);
+        if (q.inst_model) return fail(dwbc_plan::kInstModelGc);
         if (!dwbc_plan::Candidates(q, dwbc_plan::kGc, b->tables, b->n_tables).pick(dwbc_plan::kWideTasks, 0u)) return fail("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
     }
     Buf &uw = b->buf[fld::kWrench];
@@ -678,9 +767,11 @@ int dwbc_batch_enable_dump(dwbc_batch *b, int on) {
     return 1;
 }
 
-// the mirrors of these slots that are newer than their device buffers, in this order
+// the mirrors of these slots that are newer than their device buffers, in this order; every launch reads the model, so the per-instance
+// body tables go first whatever the slots are
 static int send_inputs(dwbc_batch *b, std::initializer_list<int> slots) {
     bool queued = false;
+    if (!send(b, fld::kInstModel, &queued)) return 0;
     for (const int slot : slots)
         if (!send(b, slot, &queued)) return 0;
     return queued ? mark_upload(b) : 1;
@@ -736,7 +827,7 @@ static int launch(dwbc_batch *b, bool reduced) {
     io.status = b->dev<int>(fld::kStatus);
     io.diag = b->dev<int>(fld::kDiag);
     io.dump = b->dump_on ? b->d_dump : nullptr;  // (never on an fp32 batch: the planner refuses it)
-    io.body = f32 ? reinterpret_cast<const double *>(b->f_body) : b->d_body;  // real_t of the build that p.row belongs to
+    io.body = f32 ? reinterpret_cast<const double *>(b->f_body) : launch_body(b);  // real_t of the build that p.row belongs to
     io.topo = b->d_topo;
     io.hqp = b->hqp;
     io.pair_swap_bit = p.pair_swap_bit;
@@ -882,7 +973,7 @@ static BatchIO lean_io(const dwbc_batch *b) {
     BatchIO io{};
     io.B = b->B;
     io.q = b->dev<double>(fld::kQ);
-    io.body = b->d_body;
+    io.body = launch_body(b);
     io.topo = b->d_topo;
     io.pair_swap_bit = -1;
     return io;
@@ -1018,6 +1109,7 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     wait_uploads(dst);  // the target's mirrors are rewritten below
     if (dst->su.n_contacts != src->su.n_contacts) drop_instance_params(dst);  // (never copied; the target's own goes with its stride)
     drop_task_space(dst);  // (the task levels come with the set-up)
+    // (the per-instance body tables are never copied either: the model is no kinematics data, and the target keeps its own)
     dst->su = src->su;
     Buf &dq = dst->buf[fld::kQ];
     const Buf &sq = src->buf[fld::kQ];

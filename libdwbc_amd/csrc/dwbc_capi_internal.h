@@ -100,8 +100,9 @@ struct dwbc_batch {
     bool ws_valid = false;  // diag holds the working sets of a full-build launch
     bool last_reduced = false;  // mode of the most recent dwbc_batch_solve (the LQP / JACC entry points need the matching cycle)
     // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32, the task-space kernels of a translation
-    // unit of their own), then the loaded pack of the model's own tree, then the generic pack of its size -- resolved once, at creation
-    dwbc_plan::Table tables[5] = {};
+    // unit of their own, the per-instance-model build), then the loaded pack of the model's own tree, then the generic pack of its size --
+    // resolved once, at creation
+    dwbc_plan::Table tables[6] = {};
     int n_tables = 0;
     bool tree_match = false;  // tables[] holds a pack compiled for this model's parent table
     dwbc_plan::Plan last{};   // plan of the last accepted launch (row == nullptr: none yet): kernel_name / launch_info report it

@@ -1264,7 +1264,7 @@ DWBC_DEV void cycle_instance_v2(Thr th, const Setup &su, const BatchIO &io, int 
     // a constant tree fixes the body count and the depth as well (the launcher checked the model against it)
     constexpr bool kTree = !std::is_same<Topo, TopoGeneric>::value;
     const int nb = kTree ? NB : su.nb;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;  // parent[nb] depth[nb] subtree[nb]
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     const DumpLayout dl = DumpLayout::make(N);

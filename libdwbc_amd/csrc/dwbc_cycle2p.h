@@ -351,7 +351,7 @@ DWBC_DEV void cycle_instance_v2p(int wave, Thr th, const Setup &su, const BatchI
     DWBC_LANE_DECL;
     const bool is_main = wave <= 0, is_help = wave != 0;
     const int nb = NB;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     int *diag = io.diag ? io.diag + (size_t)inst * DG_COUNT : nullptr;

@@ -378,7 +378,7 @@ DWBC_DEV void cycle_instance_gc(Thr th, const Setup &su, const BatchIO &io, int 
     using S = LdsG<N, NB, NCC, TG>;
     constexpr int M = S::M, C = S::C, T = S::T, QN = S::QN;
     const int nb = su.nb;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;  // parent[nb] depth[nb] subtree[nb]
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     int *diag = io.diag ? io.diag + (size_t)inst * DG_COUNT : nullptr;

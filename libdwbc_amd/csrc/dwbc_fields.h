@@ -19,7 +19,9 @@ enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, k
             kLqPos, kLqRot, kLqVel, kLqJac, kGvTau, kGvWrench, kGvStatus, kDyA, kDyAInv, kDyB, kDyG, kDyCmm, kDyCom, kDyStatus,
             kCoJC, kCoLambda, kCoJCInvT, kCoNC, kCoAInvNC, kCoW, kCoWInv, kCoNwJw, kCoPos, kCoRot, kCoStatus,
             // the task-space launch: output `what` of level l in slot kTsFirst + what * kMaxLevels + l, then the one status
-            kTsFirst, kTsStatusSlot = kTsFirst + 4 * kMaxLevels, kSlotCount };
+            kTsFirst, kTsStatusSlot = kTsFirst + 4 * kMaxLevels,
+            kInstModel,  // the per-instance body tables (dwbc_batch_set_instance_model): an input that is no field, like kInstPar
+            kSlotCount };
 
 // one extent of a shape: mul * var + add
 enum Var { kOne, kN, kM, kNc, kContacts, kFstarTotal, kActive, kDumpTotal, kQueried, kTaskDof };

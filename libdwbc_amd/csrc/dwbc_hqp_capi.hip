@@ -416,6 +416,8 @@ static int formulation_cfg(dwbc_batch *b, dwbc_hqp *h, LqpCfg &cfg, bool reduced
     if (cfg.nc < 1) return fail("LQP / JACC: no active contact");
     if (b->buf[dwbc_fields::kInstPar].d || !b->buf[dwbc_fields::kInstPar].h.empty())
         return fail("LQP / JACC: per-instance parameters are not built here (the formulation takes one set of contact constants for the batch): drop them with dwbc_batch_set_instance_params(b, NULL)");
+    if (b->buf[dwbc_fields::kInstModel].d || !b->buf[dwbc_fields::kInstModel].h.empty())
+        return fail("LQP / JACC: a per-instance model is not built here (the formulation reads the dump record of the batch's one model): drop it with dwbc_batch_set_instance_model(b, NULL)");
     cfg.cd = 6 * cfg.nc;
     cfg.fstar_total = b->su.fstar_total;
     cfg.tlim = 200.0;  // `tlim`, src/dwbc.cpp:4360

@@ -174,8 +174,15 @@ static_assert(sizeof(BatchIO) == 8 + 15 * sizeof(void *) + 4 * sizeof(int) && of
 namespace lp = dwbc_plan;
 #define DWBC_STR_(...) #__VA_ARGS__
 #define DWBC_STR(...) DWBC_STR_(__VA_ARGS__)
+// a DWBC_INST_MODEL build (dwbc_kernels_im.h) marks every row it emits: the planner hands such a row to a batch with a per-instance body
+// table and to no other
+#ifdef DWBC_INST_MODEL
+#define DWBC_ROW_BUILD_FLAVOUR lp::kInstModel
+#else
+#define DWBC_ROW_BUILD_FLAVOUR 0u
+#endif
 #define DWBC_ROW(N, NB, NLV, TOPO_KIND, KIND, FLAVOUR, LDS, THREADS, KERNEL, ...)                                           \
-    lp::Row{N, NB, NLV, TOPO_KIND, kF32 ? lp::kFloat : lp::kDouble, lp::KIND, FLAVOUR,                                      \
+    lp::Row{N, NB, NLV, TOPO_KIND, kF32 ? lp::kFloat : lp::kDouble, lp::KIND, (FLAVOUR) | DWBC_ROW_BUILD_FLAVOUR,           \
             reinterpret_cast<const void *>(&dwbc::KERNEL<__VA_ARGS__>), (int)LDS, THREADS, DWBC_STR(dwbc::KERNEL), DWBC_STR(__VA_ARGS__)}
 // capped extras, wide extras and wide lean build of one model size, level count and tree (TK: Row::topo of TOPO); the capped lean
 // build is laid out on the compact map (Lds3) for TOCABI's tree and on Lds2 in the packs

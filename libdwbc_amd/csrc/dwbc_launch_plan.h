@@ -20,7 +20,8 @@ enum : unsigned {
     kLean = 2,       // EXTRAS = false: none of the optional paths
     kCompact = 4,    // the 20 KB LDS map (Lds3)
     kTwoWave = 8,    // two wavefronts per instance (dwbc_cycle2p.h)
-    kWideTasks = 16  // general-contact cycle sized for task levels of up to 12 dof (TG = 12)
+    kWideTasks = 16, // general-contact cycle sized for task levels of up to 12 dof (TG = 12)
+    kInstModel = 32  // built with DWBC_INST_MODEL (namespace dwbc_im): BatchIO::body holds one body table per instance
 };
 
 struct Row {  // one launchable kernel
@@ -80,6 +81,9 @@ struct Request {
     // not a cycle either: SetTaskSpace + CalcTaskSpace on their own (dwbc_batch_calc_task_space); of the members above it reads the model,
     // arith, max_active, levels, wide_tasks and n_custom
     bool task_space = false;
+    // the batch carries one body table per instance (dwbc_batch_set_instance_model / dwbc_batch_bind_instance_model): a request is served by
+    // rows with kInstModel and by no others, so every route below picks the dwbc_im:: twin of the kernel it would pick without the record
+    bool inst_model = false;
 };
 
 struct Plan {
@@ -101,7 +105,7 @@ struct Candidates {
     bool specific = false;
     bool usable(const Row &r) const {
         return r.n == q.n && r.nb == q.nb && r.arith == q.arith && r.kind == kind && (r.nlv == 0 || r.nlv == q.levels) &&
-               (r.topo == 0 || (r.topo == 2 ? q.tree_match : r.topo == q.topo));
+               ((r.flavour & kInstModel) != 0) == q.inst_model && (r.topo == 0 || (r.topo == 2 ? q.tree_match : r.topo == q.topo));
     }
     Candidates(const Request &q_, int kind_, const Table *tabs, int n_tabs) : q(q_), kind(kind_) {
         for (int t = 0; t < n_tabs && !tab; t++)
@@ -120,12 +124,27 @@ struct Candidates {
     }
 };
 
+// what a request with a per-instance body table is refused with (after every refusal the same request meets without the record)
+constexpr const char *kInstModelReduced = "per-instance model: not built on the reduced dynamics path (drop the record with dwbc_batch_set_instance_model(b, NULL))";
+constexpr const char *kInstModelGc = "per-instance model: not built for three active contacts or task levels of more than 6 dof (the general-contact kernel has no such build)";
+constexpr const char *kInstModelNone =
+    "per-instance model: no kernel for this request (built for fp64 batches on TOCABI's constant tree: the full-model cycle of 1 to 4 task levels on every "
+    "launch route, and the redistribution, gravity-compensation, link-query, dynamics, contact-space and task-space launches)";
+
 inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
     Plan p{nullptr, 0, 0, false, -1, nullptr};
     auto refuse = [&](const char *why) {
         p.err = why;
         return p;
     };
+    // with a record: whatever refuses the request without it refuses it first, in the same words
+    if (q.inst_model) {
+        Request base = q;
+        base.inst_model = false;
+        const Plan pb = plan(base, tabs, n_tabs);
+        if (!pb.row) return pb;
+    }
+    auto none = [&](const char *why) { return refuse(q.inst_model ? kInstModelNone : why); };
     auto run = [&](const Row *r, bool ws_valid_after) {
         p.row = r;
         p.threads = r->threads;
@@ -137,7 +156,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
     if (q.link_query) {
         if (q.arith == kFloat) return refuse("link query: fp64 batches only");
         const Row *r = Candidates(q, kLinkQuery, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no link-query kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
+        if (!r) return none("no link-query kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
         return run(r, false);
     }
     // dynamics of UpdateKinematics: one kernel per model size and tree, whatever the batch size, the contact and task set-up or the cycle's
@@ -145,7 +164,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
     if (q.dynamics) {
         if (q.arith == kFloat) return refuse("dynamics: fp64 batches only");
         const Row *r = Candidates(q, kDynamics, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no dynamics kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (!r) return none("no dynamics kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         return run(r, false);
     }
     // gravity compensation: planned like the redistribution below, whatever the batch size, the levels or the cycle's options are
@@ -153,7 +172,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.arith == kFloat) return refuse("gravity compensation: fp64 batches only");
         if (q.max_active > 2) return refuse("gravity compensation: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
         const Row *r = Candidates(q, kGravComp, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no gravity-compensation kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (!r) return none("no gravity-compensation kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         return run(r, false);
     }
     // redistribution of a caller-supplied torque: one lean kernel, whatever the batch size or the task set-up (it runs no task level and
@@ -162,7 +181,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.arith == kFloat) return refuse("redistribution of a supplied torque: fp64 batches only");
         if (q.max_active > 2) return refuse("redistribution of a supplied torque: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
         const Row *r = Candidates(q, kRedist, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no redistribution kernel for this model (built in for TOCABI's size and tree; kernel packs do not carry one)");
+        if (!r) return none("no redistribution kernel for this model (built in for TOCABI's size and tree; kernel packs do not carry one)");
         if (!q.hqp) return refuse("redistribution of a supplied torque: hqp = true only (the closed form of src/dwbc.cpp:1570-1619 is not built for a supplied torque)");
         return run(r, false);
     }
@@ -171,7 +190,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.arith == kFloat) return refuse("contact space: fp64 batches only");
         if (q.max_active > 2) return refuse("contact space: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
         const Row *r = Candidates(q, kContactSpace, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no contact-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (!r) return none("no contact-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         if (q.n_contacts < 1) return refuse("contact space: no contact constraint (call dwbc_batch_add_contact first)");
         return run(r, false);
     }
@@ -182,26 +201,28 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         if (q.wide_tasks) return refuse("task space: task levels of at most 6 dof");
         if (q.n_custom > 0) return refuse("task space: TASK_CUSTOM levels are not built (their J_task is the caller's own)");
         const Row *r = Candidates(q, kTaskSpace, tabs, n_tabs).pick(0u, 0u);
-        if (!r) return refuse("no task-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
+        if (!r) return none("no task-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         if (q.levels < 1) return refuse("task space: no task level (call dwbc_batch_add_task first)");
         return run(r, false);
     }
     // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the
     // synthetic COM link; QPs start cold and keep no working sets)
     if (q.max_active > 2 || q.wide_tasks) {
+        if (q.inst_model) return refuse(kInstModelGc);
         if (q.reduced) return refuse("three active contacts / task levels of more than 6 dof: not built on the reduced dynamics path");
         if (q.arith == kFloat) return refuse("three active contacts / task levels of more than 6 dof: fp64 batches only");
         const Candidates gc(q, kGc, tabs, n_tabs);
         const Row *r = gc.pick(kWideTasks, 0);
-        if (!r) return refuse("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
+        if (!r) return none("no general-contact kernel for this model size (built in for TOCABI; kernel packs carry one for models of at most 40 dof)");
         if (q.wide_tasks && !(r = gc.pick(kWideTasks, kWideTasks))) return refuse("task levels of more than 6 dof: built in for TOCABI's size only");
         if (!q.hqp) return refuse("three active contacts / task levels of more than 6 dof: hqp = true only (the reference's closed-form redistribution is written for two contacts, src/dwbc.cpp:1570-1619)");
         if (q.n_traj > 0 || q.n_custom > 0 || q.dump_on)
             return refuse("three active contacts / task levels of more than 6 dof: link and COM tasks with f* from SetTaskSpace only (no trajectories, no TASK_CUSTOM levels, no dump record)");
         return run(r, false);
     }
+    if (q.inst_model && q.reduced) return refuse(kInstModelReduced);
     const Candidates c(q, q.reduced ? kReduced : kCycle, tabs, n_tabs);
-    if (!c.tab) return refuse(q.arith == kFloat ? "no fp32 kernel for this model / number of task levels" : "no kernel for this model / number of task levels");
+    if (!c.tab) return none(q.arith == kFloat ? "no fp32 kernel for this model / number of task levels" : "no kernel for this model / number of task levels");
     if (q.arith == kFloat && q.dump_on) return refuse("the dump record is not available on DWBC_F32 batches");
     // the lean build (EXTRAS = false) serves every launch that uses none of the optional paths
     const bool lean_asked = q.hqp && !q.warm && q.n_traj == 0 && !q.has_com_task && q.n_custom == 0 && !q.dump_on && !q.no_lean;
@@ -215,7 +236,7 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
     if ((wide || q.pair_always) && lean && !q.reduced && q.arith == kDouble && !q.no_pair) r = c.pick(kTwoWave, kTwoWave);
     const bool two_wave = r != nullptr;
     if (!r) r = c.pick(kWide | kLean | kTwoWave, (wide ? kWide : 0u) | (lean ? kLean : 0u));
-    if (!r) return refuse("no kernel for this model / number of task levels");
+    if (!r) return none("no kernel for this model / number of task levels");
     // per-instance parameters shape QP rows: the reduced path refuses a torque limit already, and the closed form of hqp = false knows neither
     // limits nor cones (a randomisation that is silently ignored is worse than a refusal)
     if (q.inst_par && q.reduced) return refuse("per-instance parameters: not built on the reduced dynamics path (drop them with dwbc_batch_set_instance_params(b, NULL))");

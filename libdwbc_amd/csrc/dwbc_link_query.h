@@ -70,7 +70,7 @@ DWBC_DEV void link_query_instance(Thr th, const BatchIO &io, const LinkQueryIO &
     static_assert(NB <= 64 && N <= 64, "one body and one dof per lane");
     DWBC_LANE_DECL;
     const int nb = lq.nb, ne = lq.n;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;  // parent[nb] depth[nb] subtree[nb]
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     const io_t *qd = io.qdot ? io.qdot + (size_t)inst * N : nullptr;

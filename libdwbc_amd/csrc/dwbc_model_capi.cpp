@@ -50,4 +50,13 @@ dwbc_model *dwbc_model_change_link_inertia(const dwbc_model *m, int link, const 
     return finish(mm, mm->m.change_link_inertia(link, com_inertia, com_position, com_mass, err), err);
 }
 
+// the device body table of the model, nb x 25 doubles (the record dwbc_batch_set_instance_model takes once per instance)
+int dwbc_model_body_table(const dwbc_model *m, double *out) {
+    if (!m || !out) { capi_err() = "NULL argument"; return 0; }
+    std::vector<double> t;
+    m->m.body_table(t);
+    memcpy(out, t.data(), t.size() * sizeof(double));
+    return 1;
+}
+
 }  // extern "C"

@@ -181,7 +181,7 @@ DWBC_DEV void redistribute_instance(Thr th, const Setup &su, const BatchIO &io, 
     DWBC_LANE_DECL;
     constexpr bool kTree = !std::is_same<Topo, TopoGeneric>::value;
     const int nb = kTree ? NB : su.nb;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;  // parent[nb] depth[nb] subtree[nb]
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     const DumpLayout dl = DumpLayout::make(N);

@@ -267,7 +267,7 @@ DWBC_DEV void cycle_instance_reduced(Thr th, const Setup &su, const BatchIO &io,
     (void)iL;
     constexpr bool kTree = !std::is_same<Topo, TopoGeneric>::value;
     const int nb = kTree ? NB : su.nb;
-    const real_t *body = io.body;
+    const real_t *body = DWBC_BODY(io, inst, nb);
     const int *topo = io.topo;
     const io_t *qin = io.q + (size_t)inst * (N + 1);
     const DumpLayout dl = DumpLayout::make(N);

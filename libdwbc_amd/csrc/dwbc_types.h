@@ -1,6 +1,7 @@
 // dwbc_types.h -- POD structures shared by the host C-ABI layer and the HIP kernels.
 // MI355X-native batched libdwbc hot path; see DESIGN.md.  No torch / Eigen types here.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -32,6 +33,16 @@ constexpr int kBodyStride = 25;       // doubles per body in the device model ta
 
 // per-body record (doubles): R_T[9] p_T[3] axis[3] mass com[3] Icom[6]{xx,xy,xz,yy,yz,zz}
 enum BodyField { BF_RT = 0, BF_PT = 9, BF_AXIS = 12, BF_MASS = 15, BF_COM = 16, BF_ICOM = 19 };
+
+// the body table an instance is computed with: BatchIO::body itself, one table for the batch.  A build with DWBC_INST_MODEL
+// (dwbc_kernels_im*.hip, namespace dwbc_im) is handed B tables back to back through the same member and takes the instance's own
+// (the host emulation of tests/emu/emu_inst_model.py predefines the macro to build its mutants; nothing else may)
+#if defined(DWBC_BODY)
+#elif defined(DWBC_INST_MODEL)
+#define DWBC_BODY(io, inst, nb) ((io).body + (size_t)(inst) * (nb) * kBodyStride)
+#else
+#define DWBC_BODY(io, inst, nb) ((io).body)
+#endif
 
 // task link modes -- same numbering as reference include/dwbc_task.h:23-33
 enum TaskMode {

@@ -107,6 +107,17 @@ class RlWBCBridge:
     def getTorqueCommand(self):
         return self.wbc.get("tau_total").astype(np.float32)
 
+    def set_instance_model(self, tables):
+        """No counterpart in the reference (one bridge, one robot): one body table per environment, (n_envs, nb, 25) as
+        ``self.model.instance_model(n_envs, mass=..., com=..., inertia=..., p_T=...)`` packs it -- every later CalcTorque() computes
+        environment i with table i.  A torch CUDA tensor is bound and read in place (rewrite it between steps at will), a numpy array is
+        checked and uploaded with the next launch; None drops the record."""
+        if tables is not None and not isinstance(tables, np.ndarray) and getattr(tables, "is_cuda", False):
+            self.wbc.bind_instance_model(tables)  # (takes the place of an uploaded record)
+            return
+        self.wbc.bind_instance_model(None)
+        self.wbc.set_instance_model(tables)
+
     def status(self):
         """Per-env return flags of the cycle (bit meanings: include/dwbc_batch.h)."""
         return self.wbc.get("status")
