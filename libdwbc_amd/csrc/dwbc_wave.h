@@ -235,45 +235,41 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long x)
     const int hi = __builtin_amdgcn_readlane((int)(unsigned)(x >> 32), 63);
     return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
 }
-// same reduction restricted to DPP row 1 (lanes 16..31); the result is read from lane 31
+// same reduction restricted to DPP row 1 (lanes 16..31), as an exact two-stage lexicographic minimum of (high word, low word) on 32-bit
+// DPP minima (v_min_u32 is VOP2: shift and minimum are one instruction).  Stage 1: row_ror:1/2/4/8 leave the row minimum of the high
+// words in EVERY lane of the row (a rotation has a source for every lane, and a minimum may take an element twice); lanes whose high word
+// is not that minimum leave the contest with a low word of all ones -- above every low word of a key, whose bits 7..31 cannot all be set
+// together with a lane below 64.  Stage 2: row_shr:1/2/4/8 bring the minimum of the remaining low words to lane 31 (a lane without a source
+// keeps its value).  Same winner, same bits as the 64-bit compare.  Each step reads by DPP what the step before wrote: `s_nop 1` ahead of it.
+#define DWBC_DPP_MIN4_(op, c0, c1, c2, c3)                                                                 \
+    "s_nop 1\n" op " %0, %0, %0 " c0 " row_mask:0xf bank_mask:0xf\n"                                       \
+    "s_nop 1\n" op " %0, %0, %0 " c1 " row_mask:0xf bank_mask:0xf\n"                                       \
+    "s_nop 1\n" op " %0, %0, %0 " c2 " row_mask:0xf bank_mask:0xf\n"                                       \
+    "s_nop 1\n" op " %0, %0, %0 " c3 " row_mask:0xf bank_mask:0xf"
 __device__ __forceinline__ unsigned long long row1_min_u64(unsigned long long x) {
-#define DWBC_DPP_STEP(ctrl)                                                                                \
-    {                                                                                                      \
-        const int lo_ = (int)(unsigned)(x & 0xffffffffull), hi_ = (int)(unsigned)(x >> 32);                \
-        const int olo_ = __builtin_amdgcn_update_dpp(lo_, lo_, ctrl, 0xf, 0xf, false);                     \
-        const int ohi_ = __builtin_amdgcn_update_dpp(hi_, hi_, ctrl, 0xf, 0xf, false);                     \
-        const unsigned long long o_ = ((unsigned long long)(unsigned)ohi_ << 32) | (unsigned)olo_;         \
-        x = o_ < x ? o_ : x;                                                                               \
-    }
-    DWBC_DPP_STEP(0x111)
-    DWBC_DPP_STEP(0x112)
-    DWBC_DPP_STEP(0x114)
-    DWBC_DPP_STEP(0x118)
-#undef DWBC_DPP_STEP
-    const int lo = __builtin_amdgcn_readlane((int)(unsigned)(x & 0xffffffffull), 31);
-    const int hi = __builtin_amdgcn_readlane((int)(unsigned)(x >> 32), 31);
-    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+    const unsigned lo = (unsigned)(x & 0xffffffffull), hi = (unsigned)(x >> 32);
+    unsigned mh = hi;
+    asm volatile(DWBC_DPP_MIN4_("v_min_u32_dpp", "row_ror:1", "row_ror:2", "row_ror:4", "row_ror:8") : "+v"(mh));
+    unsigned ml = hi == mh ? lo : 0xffffffffu;
+    asm volatile(DWBC_DPP_MIN4_("v_min_u32_dpp", "row_shr:1", "row_shr:2", "row_shr:4", "row_shr:8") : "+v"(ml));
+    const unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)ml, 31);
+    const unsigned rh = (unsigned)__builtin_amdgcn_readlane((int)mh, 31);
+    return ((unsigned long long)rh << 32) | rl;
 }
-// lane of the wave minimum of a value rounded to float: six single-register DPP steps and a ballot
+// lane of the wave minimum of a value rounded to float: six one-instruction DPP minima (v_min_f32 is VOP2) and a ballot.  bound_ctrl is
+// off: a lane without a source, or in a row the mask leaves out, keeps its value.
 __device__ __forceinline__ int wave_argmin_f32(real_t v) {
     const float f = (float)v;
     float m = f;
-#define DWBC_DPP_STEP(ctrl, rmask)                                                                         \
-    {                                                                                                      \
-        const int o_ = __builtin_amdgcn_update_dpp(__float_as_int(m), __float_as_int(m), ctrl, rmask, 0xf, false); \
-        m = fminf(m, __int_as_float(o_));                                                                  \
-    }
-    DWBC_DPP_STEP(0x111, 0xf)
-    DWBC_DPP_STEP(0x112, 0xf)
-    DWBC_DPP_STEP(0x114, 0xf)
-    DWBC_DPP_STEP(0x118, 0xf)
-    DWBC_DPP_STEP(0x142, 0xa)
-    DWBC_DPP_STEP(0x143, 0xc)
-#undef DWBC_DPP_STEP
+    asm volatile(DWBC_DPP_MIN4_("v_min_f32_dpp", "row_shr:1", "row_shr:2", "row_shr:4", "row_shr:8") "\n"
+                 "s_nop 1\nv_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n"   // row minima into rows 1 and 3
+                 "s_nop 1\nv_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"      // into rows 2 and 3 -> lane 63: the wave minimum
+                 : "+v"(m));
     const float mall = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), 63));
     const unsigned long long b = __ballot(f == mall);
     return b ? (int)__builtin_ctzll(b) : 0;
 }
+#undef DWBC_DPP_MIN4_
 // sum over the wave of a per-lane value (DPP row shifts + row broadcasts; lanes without a source add zero), result uniform
 __device__ __forceinline__ double wave_sum_f64(double x) {
 #define DWBC_DPP_STEP(ctrl, rmask)                                                                         \
@@ -449,14 +445,23 @@ __device__ __forceinline__ void rowbc_axpy(double (&a)[NA], double x, double c) 
 #undef DWBC_RB_AXPY_
 // DPP row 0 copied to rows 1 - 3: v_permlane16_swap exchanges the odd rows of its first operand with the even rows of the second (on two
 // copies of x: rows 0 0 2 2), v_permlane32_swap the upper half of the first with the lower half of the second (rows 0 0 0 0); both
-// halves of the double.  Builtins: the compiler pads their hazard itself.
+// halves of the double in ONE statement.  A swap must be two wait states behind the VALU instruction that wrote either of its operands:
+// the copies of the two dwords are made side by side, so one `s_nop 0` per pair of swaps completes the distance (the copies themselves
+// put it between the swaps and whatever wrote x).
 __device__ __forceinline__ double row_replicate(double x) {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const auto l32 = __builtin_amdgcn_permlane32_swap(l16[0], l16[0], false, false);
-    const auto h32 = __builtin_amdgcn_permlane32_swap(h16[0], h16[0], false, false);
-    return __hiloint2double((int)h32[0], (int)l32[0]);
+    unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x), tl, th;
+    asm volatile("v_mov_b32 %2, %0\n"
+                 "v_mov_b32 %3, %1\n"
+                 "s_nop 0\n"
+                 "v_permlane16_swap_b32 %0, %2\n"
+                 "v_permlane16_swap_b32 %1, %3\n"
+                 "v_mov_b32 %2, %0\n"
+                 "v_mov_b32 %3, %1\n"
+                 "s_nop 0\n"
+                 "v_permlane32_swap_b32 %0, %2\n"
+                 "v_permlane32_swap_b32 %1, %3"
+                 : "+v"(lo), "+v"(hi), "=&v"(tl), "=&v"(th));
+    return __hiloint2double((int)hi, (int)lo);
 }
 }  // namespace dwbc
 #define ROWBC_FMA(J, acc, x, y) dwbc::rowbc_fma<J>((acc), (x), (y))
