@@ -510,6 +510,65 @@ const char *dwbc_batch_task_space_kernel_name(const dwbc_batch *b);
 /* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
 int dwbc_batch_time_task_space(dwbc_batch *b, int steps, float *ms);
 
+/* ---- RobotData::CalcSingleTaskTorqueWithQP(ts, task_null_matrix, torque_prev, NwJw, J_C_INV_T, P_C, init) as a call of its own (reference
+ * include/dwbc.h:354, src/dwbc.cpp:941-1127): the constrained solve of ONE task level, the step CalcTaskControlTorque takes once per level
+ * (src/dwbc.cpp:830-852), for a caller that closes its own hierarchy law -- reorders or skips levels, puts a level beneath a torque of its
+ * own, or mixes its own projector into the chain.  One launch is one call of the method on every instance:
+ *   inputs    the level; torque_prev (m), required; task_null_matrix (m, m) row-major, optional: absent means the identity, as the
+ *             reference passes for level 0; f* of the level is the batch's own (dwbc_batch_set_fstar / bound DWBC_IN_FSTAR); the state, the
+ *             contact flags, the torque limit, the contact constants and the per-instance parameters are the batch's
+ *   computed  NwJw, J_C_INV_T, P_C, J_kt and Lambda_task from the state; Ntorque_task = N J_kt Lambda_task; the QP in [f_star_qp (t);
+ *             contact_qp (k)], k = max(contact dof - 6, 0), with the rows of src/dwbc.cpp:1001-1053 (2 m torque rows only with a torque limit,
+ *             10 cone rows per active contact), started cold, solved by the cycle's solver under the cycle's canon
+ * Outputs per instance (buffer slots of their own; batch-major; m = n - 6):
+ *   DWBC_TQ_F_STAR_QP (6) f64         ts.f_star_qp_, zero beyond t
+ *   DWBC_TQ_CONTACT_QP (6) f64        ts.contact_qp_, zero beyond k
+ *   DWBC_TQ_TORQUE_H (m) f64          J_kt Lambda (f* + f_star_qp)              (src/dwbc.cpp:839)
+ *   DWBC_TQ_TORQUE_NULL_H (m) f64     N torque_h: what is added to torque_task_ (:840, :849)
+ *   DWBC_TQ_TORQUE_CONTACT (m) f64    NwJw contact_qp, zero when k = 0         (:851)
+ *   DWBC_TQ_STATUS (1) i32            always written
+ * Status 1: the QP solved.  0: the reference's failure (src/dwbc.cpp:1117-1125) and whatever makes the task-space launch answer 0 -- more
+ * flags set than two (device-resident flags), a failed Lambda_c, a bad pivot of the W sweep, a rejected t x t block -- and every other
+ * output of that instance is zero.
+ * The launch names no buffer of dwbc_batch_solve or of the other lean launches.  dwbc_batch_add_task / _add_custom_task / _clear_tasks drop
+ * the request and the inputs.
+ * Refused (dwbc_last_error), in this order, before anything is launched: DWBC_F32 batches; dwbc_batch_set_max_active_contacts above 2; a
+ * level of more than 6 dof; a TASK_CUSTOM level; a model without the kernel (built in for TOCABI's size on its own tree and on any; kernel
+ * packs do not carry one); a batch without a task level -- all six at dwbc_batch_set_task_qp already.  Further: an unknown bit; a level out
+ * of range; a level that carries a trajectory (its f* is formed on the device, not read from DWBC_IN_FSTAR); a launch without a request or
+ * without torque_prev; a bound buffer or a host buffer of the wrong size; dwbc_batch_set_task_qp_inputs on an input that is bound; get / bind
+ * of an output that was not asked for; a get before the first launch of the request.
+ * Not built: kernel packs, fp32, three contacts, levels wider than 6 dof, TASK_CUSTOM levels, warm starts, the reduced path, the facade. */
+enum dwbc_task_qp_output {
+    DWBC_TQ_F_STAR_QP = 0, DWBC_TQ_CONTACT_QP = 1, DWBC_TQ_TORQUE_H = 2, DWBC_TQ_TORQUE_NULL_H = 3, DWBC_TQ_TORQUE_CONTACT = 4, DWBC_TQ_STATUS = 5
+};
+enum dwbc_task_qp_input { DWBC_TQ_IN_TORQUE_PREV = 0, DWBC_TQ_IN_NULL = 1 };
+/* output `index` of the launch for a model of n dof, as dwbc_lean_output_describe answers for the families; 0 when index is past the end.
+ * Needs no device and no batch. */
+int dwbc_task_qp_output_describe(int index, int n, dwbc_field_info *out);
+/* the level and mask: bits 1u << dwbc_task_qp_output; DWBC_TQ_STATUS is implied.  mask 0 drops the request and its output buffers.  Plans at
+ * once and allocates every output, so that the launch allocates nothing; bound outputs are let go of (bind again), earlier results are gone;
+ * the inputs stay */
+int dwbc_batch_set_task_qp(dwbc_batch *b, int level, unsigned mask);
+/* torque_prev: B x m; null: B x m x m or NULL (the identity; a null matrix set or bound before is let go of).  A host copy into a page-locked
+ * mirror, uploaded with the next launch */
+int dwbc_batch_set_task_qp_inputs(dwbc_batch *b, const double *torque_prev, const double *null_or_NULL);
+/* zero-copy: a caller-owned DEVICE buffer for one input (which: dwbc_task_qp_input) of exactly `bytes` = B m 8 (torque_prev) or B m m 8
+ * (null) bytes; device_ptr NULL lets go of the input (the null matrix: back to the identity) */
+int dwbc_batch_bind_task_qp_input(dwbc_batch *b, int which, void *device_ptr, size_t bytes);
+/* one launch, asynchronous on the batch's stream; uploads newer host mirrors of q, the contact flags, f*, the per-instance parameters and the
+ * two inputs first, like a solve */
+int dwbc_batch_calc_single_task_torque_qp(dwbc_batch *b);
+size_t dwbc_batch_task_qp_bytes(const dwbc_batch *b, int what);  /* of all B instances; 0: not asked for, no such output */
+/* synchronises the stream; bytes must be dwbc_batch_task_qp_bytes(b, what) */
+int dwbc_batch_get_task_qp(dwbc_batch *b, int what, void *host_out, size_t bytes);
+/* zero-copy: a caller-owned DEVICE buffer of `bytes` = dwbc_batch_task_qp_bytes(b, what) bytes for one output; NULL: back to the batch's own */
+int dwbc_batch_bind_task_qp(dwbc_batch *b, int what, void *device_ptr, size_t bytes);
+/* name of the kernel dwbc_batch_calc_single_task_torque_qp launches on this batch ("" and dwbc_last_error when it would be refused) */
+const char *dwbc_batch_task_qp_kernel_name(const dwbc_batch *b);
+/* K back-to-back launches of the request bracketed by HIP events, as dwbc_batch_time_solves */
+int dwbc_batch_time_task_qp(dwbc_batch *b, int steps, float *ms);
+
 /* ---- generic hierarchical-QP class for a batch: DWBC::HQP / HQP_Hierarch (reference include/dwbc_hqp.h:8-141,
  * src/dwbc_hqp.cpp).  Every level i poses  A_i y + a_i <= v (inequalities with slack), B_i y + b_i = w (equalities, least
  * squares), optional cost 1/2 y^T H y; levels are solved in sequence inside the null space of the earlier equalities.  The

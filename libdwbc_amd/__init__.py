@@ -6,7 +6,7 @@ thin Python host layer over that ABI.  It fails loudly when the library or a GPU
 from .batch import (  # noqa: F401
     CONTACT_6D, TASK_LINK_6D, TASK_LINK_6D_COM_FRAME, TASK_LINK_6D_CUSTOM_FRAME, TASK_LINK_POSITION,
     TASK_LINK_POSITION_COM_FRAME, TASK_LINK_POSITION_CUSTOM_FRAME, TASK_LINK_ROTATION, TASK_LINK_ROTATION_CUSTOM_FRAME,
-    TASK_SPACE_OUTPUTS, Batch, DwbcError, Model, build_pack,
+    TASK_QP_OUTPUTS, TASK_SPACE_OUTPUTS, Batch, DwbcError, Model, build_pack,
 )
 
 from .rl_bridge import RlWBCBridge  # noqa: F401,E402

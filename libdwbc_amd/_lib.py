@@ -135,6 +135,16 @@ SYMBOLS = [
     ("dwbc_batch_bind_task_space", _i, [_vp, _i, _i, _vp]),
     ("dwbc_batch_task_space_kernel_name", C.c_char_p, [_vp]),
     ("dwbc_batch_time_task_space", _i, [_vp, _i, C.POINTER(C.c_float)]),
+    ("dwbc_task_qp_output_describe", _i, [_i, _i, C.POINTER(FieldInfo)]),
+    ("dwbc_batch_set_task_qp", _i, [_vp, _i, C.c_uint]),
+    ("dwbc_batch_set_task_qp_inputs", _i, [_vp, _vp, _vp]),
+    ("dwbc_batch_bind_task_qp_input", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_calc_single_task_torque_qp", _i, [_vp]),
+    ("dwbc_batch_task_qp_bytes", C.c_size_t, [_vp, _i]),
+    ("dwbc_batch_get_task_qp", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_bind_task_qp", _i, [_vp, _i, _vp, C.c_size_t]),
+    ("dwbc_batch_task_qp_kernel_name", C.c_char_p, [_vp]),
+    ("dwbc_batch_time_task_qp", _i, [_vp, _i, C.POINTER(C.c_float)]),
     # link poses, velocities and Jacobians in a launch of their own
     ("dwbc_batch_set_link_query", _i, [_vp, _i, _vp, _vp, _i]),
     ("dwbc_batch_update_kinematics", _i, [_vp]),

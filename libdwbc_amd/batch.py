@@ -77,6 +77,20 @@ while (_r := describe_task_space(len(TASK_SPACE_OUTPUTS), 0, 0)) is not None:
     TASK_SPACE_OUTPUTS[_r.name.decode()] = _r.id
 
 
+def describe_task_qp(index, n):
+    """output `index` of the single-level task-QP launch (same file) for a model of n dof, None past the end"""
+    info = _lib.FieldInfo()
+    return info if _lib.load().dwbc_task_qp_output_describe(index, n, C.byref(info)) else None
+
+
+# name -> enumerator of enum dwbc_task_qp_output (a table of its own, like the task-space launch's), read from the library once; its two
+# inputs as enum dwbc_task_qp_input names them
+TASK_QP_OUTPUTS = {}
+while (_r := describe_task_qp(len(TASK_QP_OUTPUTS), 0)) is not None:
+    TASK_QP_OUTPUTS[_r.name.decode()] = _r.id
+TASK_QP_INPUTS = {"torque_prev": 0, "null": 1}
+
+
 class DwbcError(RuntimeError):
     pass
 
@@ -262,7 +276,7 @@ class Batch:
         makes it 12 dof wide: the batch then runs the general-contact kernel, which takes link and COM levels alike."""
         p = np.ascontiguousarray(point, np.float64)
         _check(self._L.dwbc_batch_add_task(self._h, int(level), int(mode), int(link), p.ctypes.data))
-        self._drop_task_space_tensors()  # (the library dropped the task-space request: its shapes follow the levels)
+        self._drop_level_tensors()  # (the library dropped the task-space and task-QP requests: their shapes and level follow the levels)
 
     def set_torque_limit(self, lim):
         if lim is None:
@@ -373,7 +387,7 @@ class Batch:
     def add_custom_task(self, level, task_dof):
         """AddTaskSpace(heirarchy, TASK_CUSTOM, task_dof) (reference include/dwbc.h:318)"""
         _check(self._L.dwbc_batch_add_custom_task(self._h, int(level), int(task_dof)))
-        self._drop_task_space_tensors()
+        self._drop_level_tensors()
 
     def set_custom_task(self, level, fstar, J):
         """SetTaskSpace(heirarchy, f*, J_task) (reference include/dwbc.h:333): fstar (B, t), J (B, t, n)"""
@@ -407,7 +421,7 @@ class Batch:
     def copy_kinematics_to(self, target):
         """RobotData::CopyKinematicsData(target) (reference include/dwbc.h:375)"""
         _check(self._L.dwbc_batch_copy_kinematics(target._h, self._h))
-        target._drop_task_space_tensors()  # (the task levels came with the set-up: the library dropped the target's task-space request)
+        target._drop_level_tensors()  # (the task levels came with the set-up: the library dropped the target's task-space and task-QP requests)
         target.n_contacts = self.n_contacts
         target._contact_consts = list(self._contact_consts)
         target._tau_lim = None if self._tau_lim is None else self._tau_lim.copy()
@@ -691,6 +705,13 @@ class Batch:
         for k in [k for k in self._keep if k.startswith("task_space_")]:
             del self._keep[k]
 
+    def _drop_level_tensors(self):
+        """the task levels changed: the library dropped the task-space request, and the task-QP request with its inputs (a new
+        task-space request alone leaves the task-QP launch's bound tensors in use: they stay held)"""
+        self._drop_task_space_tensors()
+        for k in [k for k in self._keep if k.startswith("task_qp_")]:
+            del self._keep[k]
+
     def calc_task_space(self):
         """One lean kernel on the batch's stream, asynchronous: kinematics, CRBA, the contact stage and, per task level, what the request
         asks for, from the state and the contact flags.  Reads no f*, and leaves every output of solve() and of the other lean launches as
@@ -740,6 +761,83 @@ class Batch:
 
     def time_task_space(self, steps):
         return self._time("task_space", steps)
+
+    # ---- CalcSingleTaskTorqueWithQP for one task level on its own: the constrained level solve (reference include/dwbc.h:354, src/dwbc.cpp:941-1127)
+    def set_task_qp(self, level, names=None):
+        """The task level calc_single_task_torque_qp() solves and the outputs it writes: any of "f_star_qp" (6), "contact_qp" (6),
+        "torque_h" (m), "torque_null_h" (m), "torque_contact" (m); "status" is always written; None: all of them.  An empty list drops the
+        request and its buffers, and so does every change of the task levels.  A new request has new output buffers: bind tensors after it.
+        The inputs stay."""
+        mask = 0
+        for k in (TASK_QP_OUTPUTS if names is None else names):
+            mask |= 1 << TASK_QP_OUTPUTS[k]
+        _check(self._L.dwbc_batch_set_task_qp(self._h, int(level), mask))
+        for k in TASK_QP_OUTPUTS:
+            self._keep.pop(f"task_qp_{k}", None)
+
+    def set_task_qp_inputs(self, torque_prev, null=None):
+        """torque_prev (B, m) and task_null_matrix (B, m, m) of the next calc_single_task_torque_qp(), copied into page-locked mirrors and
+        uploaded with the launch; null=None: the identity, as the reference passes for level 0.  An input bound to a tensor is refused here."""
+        t = np.ascontiguousarray(torque_prev, np.float64)
+        assert t.shape == (self.B, self.m), t.shape
+        nl = None
+        if null is not None:
+            nl = np.ascontiguousarray(null, np.float64)
+            assert nl.shape == (self.B, self.m, self.m), nl.shape
+        _check(self._L.dwbc_batch_set_task_qp_inputs(self._h, t.ctypes.data, nl.ctypes.data if nl is not None else None))
+        if null is None:
+            self._keep.pop("task_qp_in_null", None)
+
+    def bind_task_qp_input(self, name, tensor):
+        """input ``name`` ("torque_prev": (B, m); "null": (B, m, m)) read in place from a caller-owned device tensor of float64 by every later
+        launch; None lets go of it (the null matrix: back to the identity)"""
+        which, key = TASK_QP_INPUTS[name], f"task_qp_in_{name}"
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_task_qp_input(self._h, which, None, 0))
+            self._keep.pop(key, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        _check(self._L.dwbc_batch_bind_task_qp_input(self._h, which, C.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()))
+        self._keep[key] = tensor
+
+    def calc_single_task_torque_qp(self):
+        """One lean kernel on the batch's stream, asynchronous: one call of the reference method on every instance -- kinematics, CRBA, the
+        contact stage, J_kt and Lambda_task of the level, and the QP in [f_star_qp; contact_qp] with the torque-limit rows (if a limit is set)
+        and the ZMP / friction rows of the active contacts, started cold.  Reads the state, the contact flags, f* of the level
+        (set_fstar / a bound "in_fstar"), the torque limit, the contact constants, the per-instance parameters and the two inputs, and leaves
+        every output of solve() and of the other lean launches as it is."""
+        _check(self._L.dwbc_batch_calc_single_task_torque_qp(self._h))
+
+    def task_qp(self):
+        """dict of the asked-for outputs and ``status`` (B,) int32 (1: the QP solved; 0: that instance's outputs are zero) of the last
+        calc_single_task_torque_qp(); synchronises the stream"""
+        out = {}
+        for name, what in [("status", TASK_QP_OUTPUTS["status"])] + [(k, w) for k, w in TASK_QP_OUTPUTS.items() if k != "status"]:
+            if name != "status" and not self._L.dwbc_batch_task_qp_bytes(self._h, what):
+                continue  # (the status is asked for all the same: refused without a request or before the first launch)
+            r = describe_task_qp(what, self.n)
+            a = np.zeros((self.B,) + tuple(r.dims[: r.rank]), _DTYPES[r.dtype])
+            _check(self._L.dwbc_batch_get_task_qp(self._h, what, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def bind_task_qp(self, name, tensor):
+        """asked-for output ``name`` into a caller-owned device tensor (float64; "status": int32), written in place by every later launch;
+        None: back to a buffer of the batch's own"""
+        what, key = TASK_QP_OUTPUTS[name], f"task_qp_{name}"
+        if tensor is None:
+            _check(self._L.dwbc_batch_bind_task_qp(self._h, what, None, 0))
+            self._keep.pop(key, None)
+            return
+        assert tensor.is_cuda and tensor.is_contiguous()
+        _check(self._L.dwbc_batch_bind_task_qp(self._h, what, C.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()))
+        self._keep[key] = tensor
+
+    def task_qp_kernel_name(self):
+        return self._kernel_name("task_qp")
+
+    def time_task_qp(self, steps):
+        return self._time("task_qp", steps)
 
     def time_solves(self, steps, reduced=False):
         return self._time("solves", steps, SOLVE_HQP | SOLVE_INIT | (SOLVE_REDUCED if reduced else 0))

@@ -20,6 +20,7 @@ using namespace dwbc;
 
 extern "C" const dwbc_plan::Row *dwbc_f32_rows(int *count);  // launch table of the fp32 build (dwbc_kernels_f32.hip)
 extern "C" const dwbc_plan::Row *dwbc_task_space_rows(int *count);  // the built-in task-space kernels (dwbc_kernels_task_space.hip)
+extern "C" const dwbc_plan::Row *dwbc_task_qp_rows(int *count);  // the built-in single-level task-QP kernels (dwbc_kernels_task_qp.hip)
 // the kernels that read one body table per instance (dwbc_kernels_im.h), split over translation units of their own
 extern "C" const dwbc_plan::Row *dwbc_im_rows_l1(int *count);
 extern "C" const dwbc_plan::Row *dwbc_im_rows_l2(int *count);
@@ -366,6 +367,19 @@ static void drop_task_space(dwbc_batch *b) {
     b->ts.ran = false;
 }
 
+// the single-level task-QP request, its outputs and its two inputs, owned or bound, are let go of: the level they name belongs to the task levels
+static void drop_task_qp(dwbc_batch *b) {
+    if (!b->tq.mask && !b->tq.prev_set && !b->tq.null_set) return;
+    hipSetDevice(b->device);
+    wait_uploads(b);
+    for (int s = fld::kTqTorquePrev; s <= fld::kTqStatus; s++) {  // (hipFree waits for the launches that read and write them)
+        release(b->buf[s]);
+        b->buf[s].h.clear();
+        b->buf[s].dirty = false;
+    }
+    b->tq = {};
+}
+
 dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype) {
     if (!m || B < 1) { g_err = "bad arguments"; return nullptr; }
     if (dtype != DWBC_F64 && dtype != DWBC_F32) { g_err = "dtype must be DWBC_F64 or DWBC_F32"; return nullptr; }
@@ -392,6 +406,9 @@ dwbc_batch *dwbc_batch_create(const dwbc_model *m, int B, int device, int dtype)
     int n_ts = 0;
     const dwbc_plan::Row *ts = dwbc_task_space_rows(&n_ts);
     b->tables[b->n_tables++] = dwbc_plan::Table{ts, n_ts};
+    int n_tq = 0;
+    const dwbc_plan::Row *tq = dwbc_task_qp_rows(&n_tq);
+    b->tables[b->n_tables++] = dwbc_plan::Table{tq, n_tq};
     b->tables[b->n_tables++] = inst_model_table();
     for (const bool generic : {false, true}) {
         const dwbc_plan::Table t = pack_lookup(b->n, m->m.nb, clean_parents(m->m), generic);
@@ -470,6 +487,7 @@ int dwbc_batch_add_task(dwbc_batch *b, int level, int mode, int link, const doub
     std::string err;
     if (!setup_add_task(b->su, level, mode, link, point, err)) return fail(err);
     drop_task_space(b);
+    drop_task_qp(b);
     b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
     b->buf[fld::kFstar].dirty = true;
     return 1;
@@ -479,6 +497,7 @@ int dwbc_batch_add_custom_task(dwbc_batch *b, int level, int task_dof) {
     std::string err;
     if (!setup_add_custom_task(b->su, level, task_dof, err)) return fail(err);
     drop_task_space(b);
+    drop_task_qp(b);
     b->buf[fld::kFstar].h.assign(dwbc_batch_field_bytes(b, DWBC_IN_FSTAR));
     b->buf[fld::kFstar].dirty = true;
     b->buf[fld::kCustom].h.assign((size_t)b->B * b->su.n_custom * kMaxTaskDof * b->n * sizeof(double));
@@ -502,6 +521,7 @@ int dwbc_batch_set_custom_task(dwbc_batch *b, int level, const double *fstar, co
 
 int dwbc_batch_clear_tasks(dwbc_batch *b) {
     drop_task_space(b);
+    drop_task_qp(b);
     b->su.n_levels = 0;
     b->su.has_com_task = 0;
     b->su.n_custom = 0;
@@ -1109,6 +1129,7 @@ int dwbc_batch_copy_kinematics(dwbc_batch *dst, const dwbc_batch *src) {
     wait_uploads(dst);  // the target's mirrors are rewritten below
     if (dst->su.n_contacts != src->su.n_contacts) drop_instance_params(dst);  // (never copied; the target's own goes with its stride)
     drop_task_space(dst);  // (the task levels come with the set-up)
+    drop_task_qp(dst);
     // (the per-instance body tables are never copied either: the model is no kinematics data, and the target keeps its own)
     dst->su = src->su;
     Buf &dq = dst->buf[fld::kQ];
@@ -1481,6 +1502,189 @@ int dwbc_batch_time_task_space(dwbc_batch *b, int steps, float *ms) {
 const char *dwbc_batch_task_space_kernel_name(const dwbc_batch *b) {
     static thread_local char name[160];
     const dwbc_plan::Plan p = task_space_plan(b);
+    if (!p.row) { fail(p.err); return ""; }
+    dwbc_plan::format_name(*p.row, name, sizeof name);
+    return name;
+}
+
+// ---- CalcSingleTaskTorqueWithQP for one task level on its own: the lean kernel of dwbc_task_qp.h.  Its outputs are a table of their own
+// (dwbc_fields::kTaskQp), the request, the level, the "ran" flag and which inputs exist dwbc_batch::tq; what follows is the task-space
+// launch's plumbing with two inputs beside the outputs
+static_assert(kTqFstarQp == 1u << DWBC_TQ_F_STAR_QP && kTqContactQp == 1u << DWBC_TQ_CONTACT_QP && kTqTorqueH == 1u << DWBC_TQ_TORQUE_H &&
+                  kTqTorqueNullH == 1u << DWBC_TQ_TORQUE_NULL_H && kTqTorqueContact == 1u << DWBC_TQ_TORQUE_CONTACT, "TqIO::mask is 1u << dwbc_task_qp_output");
+static dwbc_plan::Plan task_qp_plan(const dwbc_batch *b) {
+    dwbc_plan::Request q = plan_request(b, false);
+    q.task_qp = true;
+    return dwbc_plan::plan(q, b->tables, b->n_tables);
+}
+// why the level cannot be solved by this launch (nullptr: it can)
+static const char *tq_level_refusal(const dwbc_batch *b, int level) {
+    if (level < 0 || level >= b->su.n_levels) return "single-level task QP: no such task level";
+    for (int j = 0; j < b->su.t_nlinks[level]; j++)
+        if (b->su.t_traj_slot[level][j] >= 0)
+            return "single-level task QP: the level carries a trajectory (its f* is formed on the device by the cycle, not read from DWBC_IN_FSTAR)";
+    return nullptr;
+}
+static size_t tq_input_bytes(const dwbc_batch *b, int which) {
+    return (size_t)b->B * b->m * (which == DWBC_TQ_IN_NULL ? b->m : 1) * sizeof(double);
+}
+
+int dwbc_task_qp_output_describe(int index, int n, dwbc_field_info *out) {
+    if (index < 0 || index >= fld::kTaskQp.count || !out) return 0;
+    const fld::LeanRow &r = fld::kTaskQpRows[index];
+    *out = fld::describe(r.id, r.name, r.type, r.shape, dwbc_field_dims{n, 0, 0, 0}, 0, true, false);
+    return 1;
+}
+
+size_t dwbc_batch_task_qp_bytes(const dwbc_batch *b, int what) {
+    const fld::Family &f = fld::kTaskQp;
+    if (what < 0 || what >= f.count || !((b->tq.mask >> what) & 1u)) return 0;
+    return (size_t)b->B * fld::elements(f.rows[what].shape, field_dims(b)) * fld::item_size(f.rows[what].type);
+}
+
+// why output `what` cannot be named (nullptr: it can)
+static const char *tq_refusal(const dwbc_batch *b, int what) {
+    const fld::Family &f = fld::kTaskQp;
+    if (what < 0 || what >= f.count) return f.unknown;
+    if (!b->tq.mask) return f.no_request;
+    if (!((b->tq.mask >> what) & 1u)) return f.not_asked;
+    return nullptr;
+}
+
+int dwbc_batch_set_task_qp(dwbc_batch *b, int level, unsigned mask) {
+    const fld::Family &f = fld::kTaskQp;
+    if (mask & ~f.all()) return fail(f.unknown_bit);
+    if (mask) {
+        const dwbc_plan::Plan p = task_qp_plan(b);
+        if (!p.row) return fail(p.err);
+        if (const char *why = tq_level_refusal(b, level)) return fail(why);
+        mask |= 1u << f.status;
+    }
+    HIP_OK(hipSetDevice(b->device));
+    for (int w = 0; w < f.count; w++) release(b->buf[f.rows[w].slot]);  // (hipFree waits for the launches that write them)
+    b->tq.mask = mask;
+    b->tq.level = mask ? level : 0;
+    b->tq.ran = false;
+    for (int w = 0; w < f.count; w++)
+        if (const size_t bytes = dwbc_batch_task_qp_bytes(b, w))
+            if (!ensure(b->buf[f.rows[w].slot], bytes)) {  // a failed allocation leaves no request behind: no launch may see a set bit without its buffer
+                for (int v = 0; v < f.count; v++) release(b->buf[f.rows[v].slot]);
+                b->tq.mask = 0;
+                b->tq.level = 0;
+                return 0;
+            }
+    return 1;
+}
+
+int dwbc_batch_set_task_qp_inputs(dwbc_batch *b, const double *torque_prev, const double *null) {
+    if (!torque_prev) return fail("single-level task QP: torque_prev is NULL");
+    Buf &up = b->buf[fld::kTqTorquePrev], &un = b->buf[fld::kTqNull];
+    if (up.bound()) return fail("single-level task QP: torque_prev is bound to a device buffer");
+    if (null && un.bound()) return fail("single-level task QP: the null matrix is bound to a device buffer");
+    HIP_OK(hipSetDevice(b->device));
+    wait_uploads(b);
+    up.h.assign(torque_prev, tq_input_bytes(b, DWBC_TQ_IN_TORQUE_PREV));
+    up.dirty = true;
+    b->tq.prev_set = true;
+    if (null) {
+        un.h.assign(null, tq_input_bytes(b, DWBC_TQ_IN_NULL));
+        un.dirty = true;
+    } else {  // the identity: nothing is read
+        release(un);  // (hipFree waits for the launches that read it)
+        un.h.clear();
+        un.dirty = false;
+    }
+    b->tq.null_set = null != nullptr;
+    return 1;
+}
+
+int dwbc_batch_bind_task_qp_input(dwbc_batch *b, int which, void *p, size_t bytes) {
+    if (which != DWBC_TQ_IN_TORQUE_PREV && which != DWBC_TQ_IN_NULL) return fail("single-level task QP: unknown input");
+    const size_t need = tq_input_bytes(b, which);
+    if (p && bytes != need) return fail("single-level task QP: the device buffer has " + std::to_string(bytes) + " bytes, the input " + std::to_string(need));
+    HIP_OK(hipSetDevice(b->device));
+    wait_uploads(b);
+    Buf &u = b->buf[which == DWBC_TQ_IN_NULL ? fld::kTqNull : fld::kTqTorquePrev];
+    release(u);
+    u.h.clear();
+    u.d = p;
+    u.dirty = false;
+    (which == DWBC_TQ_IN_NULL ? b->tq.null_set : b->tq.prev_set) = p != nullptr;
+    return 1;
+}
+
+int dwbc_batch_get_task_qp(dwbc_batch *b, int what, void *out, size_t bytes) {
+    if (const char *why = tq_refusal(b, what)) return fail(why);
+    if (!b->tq.ran) return fail(fld::kTaskQp.not_run);
+    const size_t need = dwbc_batch_task_qp_bytes(b, what);
+    if (bytes != need) return fail("single-level task QP: the host buffer has " + std::to_string(bytes) + " bytes, the output " + std::to_string(need));
+    HIP_OK(hipSetDevice(b->device));
+    HIP_OK(hipStreamSynchronize(b->stream));
+    return read_back(b, b->buf[fld::kTaskQpRows[what].slot].d, out, need);
+}
+
+int dwbc_batch_bind_task_qp(dwbc_batch *b, int what, void *p, size_t bytes) {
+    if (const char *why = tq_refusal(b, what)) return fail(why);
+    const size_t need = dwbc_batch_task_qp_bytes(b, what);
+    if (p && bytes != need) return fail("single-level task QP: the device buffer has " + std::to_string(bytes) + " bytes, the output " + std::to_string(need));
+    HIP_OK(hipSetDevice(b->device));
+    Buf &u = b->buf[fld::kTaskQpRows[what].slot];
+    release(u);
+    b->tq.ran = false;  // (what the batch's own buffer held is not in the new one)
+    if (!p) return ensure(u, need);
+    u.d = p;
+    return 1;
+}
+
+static int launch_task_qp(dwbc_batch *b, const dwbc_plan::Plan &p) {
+    BatchIO io = lean_io(b);  // the state, the flags, f*, the per-instance parameters and the model; no output of the cycle or of the other lean launches is named
+    io.flags = b->dev<unsigned char>(fld::kFlags);
+    io.fstar = b->dev<double>(fld::kFstar);
+    io.hqp = 1;
+    io.inst_par = b->dev<double>(fld::kInstPar);
+    Setup su_rec;
+    TqIO qio{};
+    qio.mask = b->tq.mask & ~(1u << DWBC_TQ_STATUS);
+    qio.level = b->tq.level;
+    qio.torque_prev = b->dev<double>(fld::kTqTorquePrev);
+    qio.null = b->tq.null_set ? b->dev<double>(fld::kTqNull) : nullptr;
+    qio.f_star_qp = b->dev<double>(fld::kTqFstarQp);
+    qio.contact_qp = b->dev<double>(fld::kTqContactQp);
+    qio.torque_h = b->dev<double>(fld::kTqTorqueH);
+    qio.torque_null_h = b->dev<double>(fld::kTqTorqueNullH);
+    qio.torque_contact = b->dev<double>(fld::kTqTorqueContact);
+    qio.status = b->dev<int>(fld::kTqStatus);
+    qio.cs_mask = kTqContactStageMask;  // of the contact stage: W^+ with what it needs, and NwJw (cs_out stays NULL)
+    void *args[] = {(void *)launch_setup(b, io, su_rec), (void *)&io, (void *)&qio};
+    if (!launch_kernel(b, p, args)) return 0;
+    b->tq.ran = true;
+    return 1;
+}
+
+// uploads whatever is pending of the state, the flags, f*, the per-instance parameters and the two inputs, launches once; *planned
+// (optional): the plan of the launch, for a caller that repeats it
+static int task_qp_once(dwbc_batch *b, dwbc_plan::Plan *planned) {
+    const dwbc_plan::Plan p = task_qp_plan(b);
+    if (!p.row) return fail(p.err);
+    if (!b->tq.mask) return fail(fld::kTaskQp.no_request);
+    if (const char *why = tq_level_refusal(b, b->tq.level)) return fail(why);  // (a trajectory may have been set on the level since the request)
+    if (!b->tq.prev_set) return fail("single-level task QP: no torque_prev (call dwbc_batch_set_task_qp_inputs or bind DWBC_TQ_IN_TORQUE_PREV first)");
+    HIP_OK(hipSetDevice(b->device));
+    if (!send_inputs(b, {fld::kInstPar, fld::kQ, fld::kFlags, fld::kFstar, fld::kTqTorquePrev, fld::kTqNull})) return 0;
+    if (b->su.n_contacts > 0 && !b->buf[fld::kFlags].d) return fail("no contact flags: call dwbc_batch_set_contact (or bind DWBC_IN_CONTACT) first");
+    if (!b->buf[fld::kFstar].d) return fail("no f*: call dwbc_batch_set_fstar (or bind DWBC_IN_FSTAR) first");
+    if (planned) *planned = p;
+    return launch_task_qp(b, p);
+}
+
+int dwbc_batch_calc_single_task_torque_qp(dwbc_batch *b) { return task_qp_once(b, nullptr); }
+int dwbc_batch_time_task_qp(dwbc_batch *b, int steps, float *ms) {
+    dwbc_plan::Plan p{};
+    return time_launches(b, steps, ms, [&] { return task_qp_once(b, &p); }, [&] { return launch_task_qp(b, p); });
+}
+const char *dwbc_batch_task_qp_kernel_name(const dwbc_batch *b) {
+    static thread_local char name[160];
+    const dwbc_plan::Plan p = task_qp_plan(b);
     if (!p.row) { fail(p.err); return ""; }
     dwbc_plan::format_name(*p.row, name, sizeof name);
     return name;

@@ -99,10 +99,10 @@ struct dwbc_batch {
     int warm = 0;           // last solve flags had DWBC_SOLVE_INIT clear
     bool ws_valid = false;  // diag holds the working sets of a full-build launch
     bool last_reduced = false;  // mode of the most recent dwbc_batch_solve (the LQP / JACC entry points need the matching cycle)
-    // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32, the task-space kernels of a translation
-    // unit of their own, the per-instance-model build), then the loaded pack of the model's own tree, then the generic pack of its size --
-    // resolved once, at creation
-    dwbc_plan::Table tables[6] = {};
+    // launch tables the planner chooses from, in its order of preference: built in (fp64, fp32, the task-space and the task-QP kernels of
+    // translation units of their own, the per-instance-model build), then the loaded pack of the model's own tree, then the generic pack of
+    // its size -- resolved once, at creation
+    dwbc_plan::Table tables[7] = {};
     int n_tables = 0;
     bool tree_match = false;  // tables[] holds a pack compiled for this model's parent table
     dwbc_plan::Plan last{};   // plan of the last accepted launch (row == nullptr: none yet): kernel_name / launch_info report it
@@ -135,6 +135,14 @@ struct dwbc_batch {
         unsigned mask = 0;
         bool ran = false;
     } ts;
+    // the same for the single-level task-QP launch (dwbc_fields::kTaskQp): the level and what dwbc_batch_set_task_qp named, with the status,
+    // and which of its two inputs exist (set through a mirror or bound); dropped when the task set-up changes
+    struct {
+        unsigned mask = 0;
+        int level = 0;
+        bool ran = false;
+        bool prev_set = false, null_set = false;
+    } tq;
     // the entries of the link query (dwbc_batch_set_link_query)
     int lq_n = 0, lq_link[16] = {};
     double lq_point[16][3] = {};

@@ -2,7 +2,7 @@
 // per-instance shape and where it lives.  Host only, no HIP header: dwbc_capi.hip derives dwbc_batch_field_bytes / get / bind_device /
 // host_ptr and dwbc_field_describe from the rows, the Python layer and the facade read them through those entry points, and
 // tests/test_field_table.py pins them.  A new field is one enumerator and one row.  A second table, at the end, does the same for the
-// outputs of the lean launches.
+// outputs of the lean launches, a third and a fourth for those of the task-space and the single-level task-QP launch.
 #pragma once
 #include <cstddef>
 
@@ -21,6 +21,8 @@ enum Slot { kQ, kFlags, kFstar, kTauIn, kTau, kWrench, kStatus, kRdTau, kRdCf, k
             // the task-space launch: output `what` of level l in slot kTsFirst + what * kMaxLevels + l, then the one status
             kTsFirst, kTsStatusSlot = kTsFirst + 4 * kMaxLevels,
             kInstModel,  // the per-instance body tables (dwbc_batch_set_instance_model): an input that is no field, like kInstPar
+            // the single-level task-QP launch: its two inputs (no field either), then its outputs in the order of enum dwbc_task_qp_output
+            kTqTorquePrev, kTqNull, kTqFstarQp, kTqContactQp, kTqTorqueH, kTqTorqueNullH, kTqTorqueContact, kTqStatus,
             kSlotCount };
 
 // one extent of a shape: mul * var + add
@@ -252,5 +254,29 @@ constexpr bool task_space_rows_in_order() {
     return true;
 }
 static_assert(task_space_rows_in_order() && kTaskSpace.count == DWBC_TS_STATUS + 1, "row i of the task-space table is enumerator i of dwbc_task_space_output");
+
+// ---- the outputs of the single-level task-QP launch (enum dwbc_task_qp_output): a table of its own, no family of kLean (that table is
+// the four launches that read the state alone; this one has inputs and a level of its own: dwbc_batch::tq).  Row i is enumerator i and lives
+// in slot kTqFstarQp + i; dwbc_capi.hip derives dwbc_batch_task_qp_bytes / get / bind and the allocation of a request from the rows, the
+// Python layer reads them through dwbc_task_qp_output_describe.
+inline constexpr LeanRow kTaskQpRows[] = {
+    {DWBC_TQ_F_STAR_QP, kTqFstarQp, "f_star_qp", F64, sh(c(T))},
+    {DWBC_TQ_CONTACT_QP, kTqContactQp, "contact_qp", F64, sh(c(K))},
+    {DWBC_TQ_TORQUE_H, kTqTorqueH, "torque_h", F64, sh(M)},
+    {DWBC_TQ_TORQUE_NULL_H, kTqTorqueNullH, "torque_null_h", F64, sh(M)},
+    {DWBC_TQ_TORQUE_CONTACT, kTqTorqueContact, "torque_contact", F64, sh(M)},
+    {DWBC_TQ_STATUS, kTqStatus, "status", I32, sh()},
+};
+inline constexpr Family kTaskQp =
+    family(kTaskQpRows, DWBC_TQ_STATUS, "single-level task QP: unknown output",
+           "single-level task QP: unknown output bit (the outputs are 1u << DWBC_TQ_F_STAR_QP .. 1u << DWBC_TQ_STATUS)",
+           "no single-level task-QP request: call dwbc_batch_set_task_qp first", "single-level task QP: this output was not asked for (dwbc_batch_set_task_qp)",
+           "no single-level task-QP output yet: call dwbc_batch_calc_single_task_torque_qp first");
+constexpr bool task_qp_rows_in_order() {
+    for (int i = 0; i < kTaskQp.count; i++)
+        if (kTaskQpRows[i].id != i || kTaskQpRows[i].slot != kTqFstarQp + i) return false;
+    return true;
+}
+static_assert(task_qp_rows_in_order() && kTaskQp.count == DWBC_TQ_STATUS + 1, "row i of the task-QP table is enumerator i of dwbc_task_qp_output");
 
 }  // namespace dwbc_fields

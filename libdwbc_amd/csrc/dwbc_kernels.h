@@ -15,6 +15,7 @@
 #include "dwbc_dynamics.h"
 #include "dwbc_contact_space.h"
 #include "dwbc_task_space.h"
+#include "dwbc_task_qp.h"
 
 namespace dwbc {
 
@@ -161,6 +162,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dw
     task_space_instance<N, NB, 64, Topo>(th, su, io, tio, inst, lds);
 }
 
+// CalcSingleTaskTorqueWithQP for one task level in a launch of its own (dwbc_task_qp.h): the task-space kernel's front for that level, the
+// operands of the QP rows and the cycle's row fill and solver -- LdsTq (37 KB at TOCABI's size: four workgroups per CU), register-capped like
+// the other lean kernels
+template <int N, int NB, class Topo>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void dwbc_task_qp_kernel(const Setup su, const BatchIO io, const TqIO qio) {
+    extern __shared__ __attribute__((aligned(16))) real_t lds[];
+    const int inst = blockIdx.x;
+    if (inst >= io.B) return;
+    Thr th{(int)threadIdx.x};
+    task_qp_instance<N, NB, 64, Topo>(th, su, io, qio, inst, lds);
+}
+
 #define DWBC_NT 64  // threads of the one-wave kernels, as a literal: the rows below spell it into the kernel names
 constexpr int kNT = DWBC_NT;
 static_assert(kMaxTaskDof == 6 && kMaxTaskDofWide == 12, "the TG arguments of the general-contact rows below");
@@ -252,6 +265,10 @@ namespace lp = dwbc_plan;
 #define DWBC_ROW_TASK_SPACE(N, NB, TOPO, TK) \
     DWBC_ROW(N, NB, 0, TK, kTaskSpace, 0u, (LdsTs<N, NB>::total_bytes), kNT, dwbc_task_space_kernel, N, NB, dwbc::TOPO),
 #endif
+// the single-level task-QP kernel: fp64, for a constant tree or any tree of the size; built in only (dwbc_kernels_task_qp.hip), no kernel
+// pack carries one
+#define DWBC_ROW_TASK_QP(N, NB, TOPO, TK) \
+    DWBC_ROW(N, NB, 0, TK, kTaskQp, 0u, (LdsTq<N, NB>::total_bytes), kNT, dwbc_task_qp_kernel, N, NB, dwbc::TOPO),
 // instantiated model sizes (system dof, bodies).  TOCABI = (39, 34), the only model in BASELINE.json's configs: its four flavours
 // and the reduced path use the constant tree; any other 34-body tree runs the TopoGeneric builds (capped extras flavour only).  Other
 // model sizes come from kernel packs (dwbc_pack.hip: this header instantiated for one (N, NB), loaded by the C-ABI at model-load time).
@@ -278,8 +295,8 @@ const lp::Row kRows[] = {
     DWBC_ROW_CONTACT_SPACE(39, 34, TopoTocabi, 1) DWBC_ROW_CONTACT_SPACE(39, 34, TopoGeneric, 0)
 };
 #endif
-// (the built-in task-space rows are emitted by a translation unit of their own, dwbc_kernels_task_space.hip: the code objects of the kernels
-// above stay the ones they were whatever that kernel grows into)
+// (the built-in task-space and task-QP rows are emitted by translation units of their own, dwbc_kernels_task_space.hip and
+// dwbc_kernels_task_qp.hip: the code objects of the kernels above stay the ones they were whatever those kernels grow into)
 
 // what a pack and the library that loads it must agree on (both are built from this header): the sizes of the shared structures
 // and a hash of the kernel sources (Makefile: DWBC_SRC_HASH), so that a pack left over from older kernel code is refused

@@ -1,4 +1,4 @@
-// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation, the dynamics of UpdateKinematics, the contact space of CalcContactConstraint or the task space of CalcTaskSpace):
+// dwbc_launch_plan.h -- which build of the cycle kernel serves a solve (and which kernel a redistribution of a caller-supplied torque, a link query, a gravity compensation, the dynamics of UpdateKinematics, the contact space of CalcContactConstraint, the task space of CalcTaskSpace or one level's task QP of CalcSingleTaskTorqueWithQP):
 // the table row of every launchable kernel and the one function that picks among them.  Host only, no HIP header: dwbc_kernels.h emits the rows (fp64, fp32 and pack builds alike),
 // dwbc_capi.hip launches what plan() returns and reports it, tests/cpp/launch_plan.cpp runs plan() over a hand-written table.
 // The namespace is not `dwbc`: the fp32 build renames that one.
@@ -14,7 +14,8 @@ enum Arith { kDouble = 0, kFloat = 1 };
 // the dynamics half of UpdateKinematics on its own (dwbc_dynamics.h)
 // SetContact + CalcContactConstraint on their own (dwbc_contact_space.h)
 // SetTaskSpace + CalcTaskSpace on their own (dwbc_task_space.h)
-enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6, kContactSpace = 7, kTaskSpace = 8 };
+// CalcSingleTaskTorqueWithQP for one task level on its own (dwbc_task_qp.h)
+enum Kind { kCycle = 0, kReduced = 1, kGc = 2, kRedist = 3, kLinkQuery = 4, kGravComp = 5, kDynamics = 6, kContactSpace = 7, kTaskSpace = 8, kTaskQp = 9 };
 enum : unsigned {
     kWide = 1,       // no register cap (one wave per SIMD): batches of at most 4 instances per CU
     kLean = 2,       // EXTRAS = false: none of the optional paths
@@ -84,6 +85,10 @@ struct Request {
     // the batch carries one body table per instance (dwbc_batch_set_instance_model / dwbc_batch_bind_instance_model): a request is served by
     // rows with kInstModel and by no others, so every route below picks the dwbc_im:: twin of the kernel it would pick without the record
     bool inst_model = false;
+    // not a cycle either: CalcSingleTaskTorqueWithQP for one task level on its own (dwbc_batch_calc_single_task_torque_qp); of the members
+    // above it reads the model, arith, max_active, levels, wide_tasks and n_custom (per-instance parameters shape its QP rows as they do the
+    // cycle's: no route changes)
+    bool task_qp = false;
 };
 
 struct Plan {
@@ -203,6 +208,17 @@ inline Plan plan(const Request &q, const Table *tabs, int n_tabs) {
         const Row *r = Candidates(q, kTaskSpace, tabs, n_tabs).pick(0u, 0u);
         if (!r) return none("no task-space kernel for this model (built in for TOCABI's size, any tree; a kernel pack carries one for its size)");
         if (q.levels < 1) return refuse("task space: no task level (call dwbc_batch_add_task first)");
+        return run(r, false);
+    }
+    // one level's task QP of CalcSingleTaskTorqueWithQP: one kernel per model size and tree, whatever the batch size, hqp, warm or the dump record are
+    if (q.task_qp) {
+        if (q.arith == kFloat) return refuse("single-level task QP: fp64 batches only");
+        if (q.max_active > 2) return refuse("single-level task QP: two simultaneously active contacts at most (call dwbc_batch_set_max_active_contacts(b, 2))");
+        if (q.wide_tasks) return refuse("single-level task QP: task levels of at most 6 dof");
+        if (q.n_custom > 0) return refuse("single-level task QP: TASK_CUSTOM levels are not built (their J_task is the caller's own)");
+        const Row *r = Candidates(q, kTaskQp, tabs, n_tabs).pick(0u, 0u);
+        if (!r) return none("no single-level task-QP kernel for this model (built in for TOCABI's size, any tree; kernel packs do not carry one)");
+        if (q.levels < 1) return refuse("single-level task QP: no task level (call dwbc_batch_add_task first)");
         return run(r, false);
     }
     // three active contacts, or a task level of more than six dof: the general-contact kernel (lean scope: link tasks and the

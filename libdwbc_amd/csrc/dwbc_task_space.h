@@ -17,6 +17,8 @@
 //   neither J_KT nor NULL_TASK   nothing behind Lambda of each level: no internal-wrench basis, no G^-1, no W^+ sweep
 //   no NULL_TASK                 no projector is formed, no m x m store
 // No f*, no trajectory, no QP; of BatchIO it reads q, flags, body and topo, of Setup the tree, the contacts and the task levels.
+// The per-level text ahead of and behind the W^+ sweep is dwbc_task_space_level_front.inc / dwbc_task_space_level_back.inc: the single-level
+// task-QP kernel (dwbc_task_qp.h) runs the same text for its one level.
 #pragma once
 #include "dwbc_contact_space.h"
 
@@ -203,34 +205,8 @@ DWBC_DEV void task_space_instance(Thr th, const Setup &su, const BatchIO &io, co
         // ================= per level, while the columns A^-1 N_c and the link positions stand: J_task, T1, Lambda_task (wbd.cpp:210) =================
         auto levels_front = [&]() __attribute__((always_inline)) {
             for (int lv = 0; lv < nlv; lv++) {
-                const int t = su.t_dof[lv];
-                const unsigned long long tm = su.t_dofmask[lv];
-                real_t *T1 = L + S::e_T1 + lv * T * N, *Lt = L + S::e_Lt + lv * T * T;
-                task_jacobian_rows<N, NB, NT>(th, su, lv, L + S::Rw0, L + S::pw, L + S::aw, topo, nb, L + S::e_Pt + lv * kMaxTaskLinks * 3, L + S::e_Jcm, Jt);
-                if (want & kTsJTask) put_j_task(lv);
-                LANES {  // T1[:, lane] = J_task (lane's column of A^-1 N_c)
-                    real_t tc_[T];
-#pragma unroll
-                    for (int r = 0; r < T; r++) tc_[r] = real_t(0.0);
-#pragma unroll
-                    for (int ib = 0; ib < N; ib += 3) {  // one uniform branch per 3 columns, as in the cycle: the zero columns of J_task are skipped
-                        if ((tm >> ib) & 7) {
-#pragma unroll
-                            for (int i = ib; i < ib + 3 && i < N; i++)
-#pragma unroll
-                                for (int r = 0; r < T; r++) tc_[r] += Jt[i * T + r] * LV(s)[i];
-                        }
-                    }
-                    if (lane < N) {
-#pragma unroll
-                        for (int r = 0; r < T; r++) T1[r * N + lane] = tc_[r];
-                    }
-                }
-                DWBC_SYNC();
-                real_t *Gl = L + S::e_G + lv * T * T;
-                mm_nn<NT>(th, Gl, t, T1, N, Jt, T, t, N, t);  // Lambda^-1 = J_task A^-1 N_c J_task^T, kept for the level's J_kt
-                if (!spd_inverse_small(Gl, t, t, Lt, t, L + S::c_s1)) st_task = 0;
-                newton_step_small<NT>(th, Gl, Lt, t, L + S::e_Pi, L + S::e_cod);
+                const int ls = lv;
+#include "dwbc_task_space_level_front.inc"
             }
         };
         // of the contact stage: kCsWInv -- the columns s <- A^-1 N_c, G^-1 and W^+ -- where J_kt or Null_task is asked for, else kCsW -- the
@@ -264,62 +240,8 @@ DWBC_DEV void task_space_instance(Thr th, const Setup &su, const BatchIO &io, co
                 for (int idx = th.tid; idx < t * t; idx += NT) o[idx] = Lt[idx];
             }
             if (!(want & kTsNeedsW)) continue;
-            for (int idx = th.tid; idx < t * M; idx += NT) {  // Q = (Lambda T1)[:, 6:]
-                const int i = idx / M, j = idx - i * M;
-                real_t acc = real_t(0.0);
-                for (int p = 0; p < t; p++) acc += Lt[i * t + p] * T1[p * N + 6 + j];
-                Q[idx] = acc;
-            }
-            DWBC_SYNC();
-            mm_nn<NT>(th, QW, M, Q, M, Wp, M, t, M, M);  // Q W^+
-            DWBC_SYNC();
-            mm_nt<NT>(th, s2, t, QW, M, Q, M, t, M, t);  // Q W^+ Q^T
-            real_t pr_ = real_t(1.0);
-            bool truncated = false;
-            int cond = spd_inverse_small(s2, t, t, Pi, t, L + S::c_s1, &pr_);  // PinvCODWB, full-rank case: the SPD inverse
-            if (cond) newton_step_small<NT>(th, s2, Pi, t, cod, cod + T * T);
-            DWBC_SYNC();
-            if (!cond || pr_ < kCodCheck) {  // as the cycle: the rank decision of the reference's complete orthogonal decomposition
-                const int rk = pinv_cod_small<NT>(th, s2, t, kCodThreshold, Pi, cod, cod + T * T, cod + 2 * T * T, cod + 3 * T * T);
-                if (rk < t) { cond = 1; truncated = true; }
-            }
-            if (!cond) { st_task = 0; break; }
-            DWBC_SYNC();
-            for (int idx = th.tid; idx < M * t; idx += NT) {  // J_kt = W^+ Q^T pinv(.) = (Q W^+)^T pinv(.), M x t
-                const int i = idx / t, j = idx - i * t;
-                real_t acc = real_t(0.0);
-                for (int r = 0; r < t; r++) acc += QW[r * M + i] * Pi[r * t + j];
-                Jk[idx] = acc;
-            }
-            DWBC_SYNC();
-            // A caller multiplies J_kt Lambda back onto Y = T1[:, 6:] (Y X = I makes I - X Y the level's projector): one step on the right
-            // inverse, X <- X - X (Y X - I), takes out what the m-long sums of Q W^+ and Q W^+ Q^T left in Y X - I (2 - 3e-13 in host emulation,
-            // five times the restatement's; behind the step, its level).  J_kt = X Lambda^-1 keeps the column space of W^+ Q^T.
-            real_t *X = Q, *U = QW;  // both dead behind J_kt
-            mm_nn<NT>(th, X, t, Jk, t, Lt, t, M, t, t);  // X = J_kt Lambda, M x t
-            DWBC_SYNC();
-            if (!truncated) {  // (a truncated pseudo-inverse has Y X != I by design)
-            for (int idx = th.tid; idx < t * t; idx += NT) {  // E = Y X - I
-                const int i = idx / t, j = idx - i * t;
-                real_t acc = (i == j) ? real_t(-1.0) : real_t(0.0);
-                for (int c = 0; c < M; c++) acc += T1[i * N + 6 + c] * X[c * t + j];
-                s2[idx] = acc;
-            }
-            DWBC_SYNC();
-            for (int i = th.tid; i < M; i += NT) {  // row i of X - X E, in place: the row is read before it is written
-                real_t xr[T], xn[T];
-                for (int j = 0; j < t; j++) xr[j] = X[i * t + j];
-                for (int j = 0; j < t; j++) {
-                    real_t acc = xr[j];
-                    for (int r = 0; r < t; r++) acc -= xr[r] * s2[r * t + j];
-                    xn[j] = acc;
-                }
-                for (int j = 0; j < t; j++) X[i * t + j] = xn[j];
-            }
-            DWBC_SYNC();
-            mm_nn<NT>(th, Jk, t, X, t, L + S::e_G + lv * T * T, t, M, t, t);  // J_kt = X Lambda^-1
-            DWBC_SYNC();
-            }
+            const int ls = lv;
+#include "dwbc_task_space_level_back.inc"
             if (want & kTsJkt) {
                 io_t *o = tio.J_kt[lv] + (size_t)inst * M * t;
                 for (int idx = th.tid; idx < M * t; idx += NT) o[idx] = Jk[idx];

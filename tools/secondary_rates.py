@@ -62,6 +62,22 @@ for B in (1024, 8192):
           f" -> {B / (t_cfg + t_sol + t_nc):9.0f} instances/s")
     del hq, hj, hr, hn, wbc, wr
 
+# one level's task QP as a lean launch (dwbc_task_qp.h): level 1 of the two-level set-up beneath the gravity torque, Null_task of level 0 from
+# the task-space launch, all outputs (tools/task_qp_rate.py sets it beside the task-space launch and the one-level cycle)
+for B in (1024, 8192):
+    wbc = make(B)
+    wbc.grav_compensation()
+    tg = wbc.grav_outputs()["tau"]
+    wbc.set_task_space_outputs(["Null_task"])
+    wbc.calc_task_space()
+    null = wbc.task_space(0)["Null_task"]
+    wbc.set_task_qp(1)
+    wbc.set_task_qp_inputs(tg, null)
+    ms = wbc.time_task_qp(200) / 200
+    print(f"B = {B:5d}  single-level task QP ({wbc.task_qp_kernel_name()}): {ms * 1e3:7.1f} us per launch -> {B / ms * 1e3 / 1e6:5.2f} M level solves/s, "
+          f"status ok {wbc.task_qp()['status'].mean():.3f}")
+    del wbc
+
 # the fused cycle on other model sizes (lean build of the pack), B = 1024
 from tests.test_model_packs import VARIANTS, model_43, variant_urdf  # noqa: E402
 
